@@ -7,13 +7,15 @@ GPU; files shard per rank with no collective on the data path (weak scaling: eve
 Prints ONE JSON line on rank 0.
 
 The headline (`value`, `ms_per_step`, `roofline`, `phases`) is the library's DEFAULT profile = what libcaesium's `-q 80` runs
-(compressor.rs:415,427 -> mozjpeg JCP_MAX_COMPRESSION): scan search + trellis quantisation + overshoot deringing.  Measured in the same run
-and carried in the line: `scalar_profile` (CSH_PROFILE=scalar: the scan search over the scalar quantiser -- the pieces pinned by j0.JPG and
-libjpeg-turbo) and `plain_profile` (stock script, whole files equal libjpeg-turbo's); a `summary` object at the FRONT of the line repeats
-the three values; `roofline` for the dominant kernel with `traffic` from two rocprofv3 --pmc passes this script starts itself (FETCH_SIZE,
-WRITE_SIZE; separate passes, no trace domain); `cpu_baseline` (the oracle on the host, same profile), `boundary` (cs_batch_compress from
-host buffers), `cli_end_to_end` (the caesiumclt binary, files in -> files out), `other_configs`
-(configs[2], configs[3], configs[4]) each with its own roofline and CPU lines.
+(compressor.rs:415,427 -> mozjpeg JCP_MAX_COMPRESSION): scan search + trellis quantisation + overshoot deringing.  A plain run does only
+what the headline needs: make the inputs, upload them, warm up, time --steps steps, write the last step's files if --dump-outputs is
+given, print the line (`kernel_ms`, `roofline` and `phases` come from the same steps' events).  With --full the same run also checks and
+measures everything else and carries it in the line: byte parity of every distinct image against the oracle, `scalar_profile`
+(CSH_PROFILE=scalar: the scan search over the scalar quantiser -- the pieces pinned by j0.JPG and libjpeg-turbo) and `plain_profile`
+(stock script, whole files equal libjpeg-turbo's); a `summary` object at the END of the line repeats the three values; the roofline's
+`traffic` from two rocprofv3 --pmc passes this script starts itself (FETCH_SIZE, WRITE_SIZE; separate passes, no trace domain);
+`cpu_baseline` (the oracle on the host, same profile), `boundary` (cs_batch_compress from host buffers), `cli_end_to_end` (the caesiumclt
+binary, files in -> files out), `other_configs` (configs[2], configs[3], configs[4]) each with its own roofline and CPU lines.
 """
 import argparse
 import json
@@ -196,7 +198,7 @@ Q80_TABLE3 = [max(1, min(32767, (v * 40 + 50) // 100)) for v in _BASE3]
 
 def _one_input(i):
     from gen_synth import synth_jpeg
-    return synth_jpeg(i)
+    return synth_jpeg(i, fast=True)   # the bytes of synth_jpeg(i), made in a quarter of the time
 
 
 def _one_png_1080(i):
@@ -215,18 +217,56 @@ def _one_webp_1080(i):
     return b.getvalue()
 
 
+def host_cpus():
+    """the CPUs this process may use: its affinity mask, no more than its cgroup's CPU quota or OMP_NUM_THREADS where either is set (a share of
+    a larger host: a pool sized by os.cpu_count() would only slow itself down)"""
+    n = len(os.sched_getaffinity(0))
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()
+        if quota != "max":
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    try:
+        n = min(n, int(os.environ["OMP_NUM_THREADS"]))
+    except (KeyError, ValueError):
+        pass
+    return max(1, n)
+
+
 def pool_map(fn, items):
     items = list(items)
     if len(items) <= 4:
         return [fn(i) for i in items]
     import multiprocessing as mp
-    with mp.get_context("fork").Pool(min(len(items), os.cpu_count() or 1, 192)) as pool:
+    with mp.get_context("fork").Pool(min(len(items), host_cpus())) as pool:
         return pool.map(fn, items, chunksize=1)
 
 
 def make_inputs(first, count):
-    """`count` distinct 1080p q92 4:2:0 baseline JPEGs (SURVEY 8d recipe, seeds first..), made on all host cores (~1.2 s of numpy each)"""
+    """`count` distinct 1080p q92 4:2:0 baseline JPEGs (SURVEY 8d recipe, seeds first..), made on the host's cores (~0.2 s each)"""
     return pool_map(_one_input, range(first, first + count))
+
+
+DUMP_FILES = 12              # --dump-outputs: files of the batch written out byte by byte (a fixed seeded sample) ...
+DUMP_FILE_BYTES = 1 << 20    # ... each up to its first MiB (float32: 4 MiB per file, 48 MiB at most)
+
+
+def dump_outputs(d, outs):
+    """--dump-outputs: the files of the last timed step as a caller of csh_batch_fetch receives them, in arrays two builds can be compared by:
+    lengths.npy and crc32.npy (float64, one entry per file of the batch, -1 for a failed file) and file_<index>.npy (float32, one value per byte)
+    for DUMP_FILES files picked by a fixed seed"""
+    import zlib
+
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    files = [o if isinstance(o, bytes) else None for o in outs]
+    np.save(os.path.join(d, "lengths.npy"), np.array([-1 if f is None else len(f) for f in files], dtype=np.float64))
+    np.save(os.path.join(d, "crc32.npy"), np.array([-1 if f is None else zlib.crc32(f) for f in files], dtype=np.float64))
+    pick = np.random.default_rng(20251015).choice(len(files), min(DUMP_FILES, len(files)), replace=False)
+    for i in sorted(pick.tolist()):
+        data = (files[i] or b"")[:DUMP_FILE_BYTES]
+        np.save(os.path.join(d, f"file_{i:05d}.npy"), np.frombuffer(data, dtype=np.uint8).astype(np.float32))
 
 
 def spawn_ranks(n):
@@ -326,7 +366,13 @@ def main():
                     "cs_batch_compress from host buffers on its own device (strong scaling; /root/reference/src/compressor.rs:81-100's par_iter as device shards)")
     ap.add_argument("--boundary-total", type=int, default=10000, help="files of the shared list of --boundary (SURVEY 8d: 10 000)")
     ap.add_argument("--same-device", action="store_true", help="--boundary: every rank uses device 0 (two ranks on one GPU: the code path of N ranks without N GPUs)")
+    ap.add_argument("--full", action="store_true", help="besides the headline, check and measure everything else: byte parity against the oracle, the scalar and plain "
+                    "profiles, the roofline kernel's rocprofv3 --pmc traffic, the CPU baselines, the boundary and caesiumclt legs, the other configs (minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the files the last one made (rank 0's batch) to DIR as .npy arrays: every "
+                    "file's length and CRC-32, and the bytes of a fixed sample of files")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.pmc_child:
         # one step of the same workload for the counter passes (live_pmc): no torch, no records
@@ -349,16 +395,25 @@ def main():
     if args.boundary:
         return boundary_main(args)
 
-    import torch
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
-    if world > 1:
-        import torch.distributed as dist
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+
+    # config 2 inputs: Pillow/libjpeg-turbo q92 4:2:0 baseline JPEGs of the SURVEY 8d synthetic images, made before this process touches the
+    # device (the pool forks)
+    nuniq = max(1, min(args.unique, args.batch))
+    uniq = make_inputs(rank * nuniq, nuniq)
+
+    # torch only for what needs it: the collectives of N ranks and the --full records; one rank's headline goes through the C ABI alone
+    torch = dist = None
+    if world > 1 or args.full:
+        import torch
+        if world > 1:
+            import torch.distributed as dist
+            os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+            torch.cuda.set_device(local)
+            dist.init_process_group("nccl", device_id=torch.device("cuda", local))
         torch.cuda.set_device(local)
-        dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-    torch.cuda.set_device(local)
 
     from _util import package
     pkg = package()
@@ -366,9 +421,6 @@ def main():
     if api.device_count() < 1:
         raise SystemExit("no HIP device: libcaesium_hip has no CPU path")
 
-    # config 2 inputs: Pillow/libjpeg-turbo q92 4:2:0 baseline JPEGs of the SURVEY 8d synthetic images
-    nuniq = max(1, min(args.unique, args.batch))
-    uniq = make_inputs(rank * nuniq, nuniq)
     blobs = [uniq[i % nuniq] for i in range(args.batch)]
     params = pkg.default_parameters(jpeg_quality=80)
     batch = api.batch(blobs, params, device=local)   # parse + upload: inputs now resident in HBM
@@ -376,7 +428,8 @@ def main():
     def barrier():
         if world > 1:
             dist.barrier()
-        torch.cuda.synchronize()
+        if torch is not None:
+            torch.cuda.synchronize()   # (csh_batch_run returns after its stream has drained: without torch there is nothing to wait for)
 
     for _ in range(args.warmup):
         batch.run()
@@ -404,21 +457,26 @@ def main():
     mp_per_step = t.pixels / 1e6 * world
     value = mp_per_step * args.steps / dt
 
-    # parity on this very batch (outside the timed region): EVERY distinct image of the batch, device output == oracle byte for byte (the all-core
-    # oracle does ~150 MP/s: 1000 files in ~14 s); the two side profiles check every 8th
-    outs = batch.fetch()
-    from _util import oracle_lossy
-    all_idx = list(range(nuniq)) if (world == 1 and not args.no_extras) else sorted({(i * nuniq) // 32 for i in range(32)} | {nuniq - 1})
+    # what the last timed step made (outside the timed region): written out for --dump-outputs; under --full, parity on this very batch: EVERY
+    # distinct image of the batch, device output == oracle byte for byte (the all-core oracle does ~150 MP/s: 1000 files in ~14 s); the two side
+    # profiles check every 8th
+    outs = batch.fetch() if args.full or (args.dump_outputs and rank == 0) else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs)
+    parity, all_idx = None, []
     parity_idx = sorted(set(range(0, nuniq, 8)) | {nuniq - 1})
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(min(len(all_idx), os.cpu_count() or 1)) as ex:   # (ctypes releases the GIL inside the oracle)
-        parity = all(ex.map(lambda i: outs[i] == oracle_lossy(blobs[i]), all_idx))
+    if args.full:
+        from _util import oracle_lossy
+        all_idx = list(range(nuniq)) if (world == 1 and not args.no_extras) else sorted({(i * nuniq) // 32 for i in range(32)} | {nuniq - 1})
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(min(len(all_idx), os.cpu_count() or 1)) as ex:   # (ctypes releases the GIL inside the oracle)
+            parity = all(ex.map(lambda i: outs[i] == oracle_lossy(blobs[i]), all_idx))
     del outs
     batch.close()   # its pools go back to the block cache: the records below make batches of their own
 
     # strong scaling at the boundary, in this same invocation (every rank takes part); then, N > 1 only, the drop-in binary over the same list on N devices
     bstrong = cli_gpus = None
-    if not args.no_extras and args.boundary_total > 0:
+    if args.full and not args.no_extras and args.boundary_total > 0:
         def reduce_max_sum(mx, sums):
             if world == 1:
                 return mx, sums
@@ -449,8 +507,8 @@ def main():
             roof.update({"achieved": round(ach, 2), "frac": round(ach / HBM_PEAK_GBS, 5), "algorithmic_bytes": int(ab)})
         else:
             roof.update({"achieved": None, "frac": None})
-        extras = world == 1 and not args.no_extras
-        if world == 1 and not args.no_pmc:
+        extras = world == 1 and args.full and not args.no_extras
+        if world == 1 and args.full and not args.no_pmc:
             api.release_cached_memory()   # the closed batch's pools sit in this process's block cache: the child needs the same 100 GB
             traffic, detail = live_pmc(names[dom], args.batch, prof_env, inputs=blobs)
             roof["traffic"] = traffic
@@ -519,7 +577,7 @@ def main():
                 cli10k = cli_end_to_end(blobs, 10000)   # BASELINE configs[1]'s own count: the cold process amortises
         def short(rec):
             return None if rec is None else {"value": rec["value"], "ms_per_step": rec["ms_per_step"], "parity": rec["parity_spot_check"]}
-        summary = {"unit": "MP/s", prof_env + " (headline)": {"value": round(value, 1), "ms_per_step": round(dt / args.steps * 1e3, 3), "parity": bool(parity)},
+        summary = {"unit": "MP/s", prof_env + " (headline)": {"value": round(value, 1), "ms_per_step": round(dt / args.steps * 1e3, 3), "parity": parity},
                    "scalar": short(scalar), "plain": short(plain), "roofline_kernel": roof["kernel"], "roofline_frac": roof.get("frac"),
                    "X_read_only_frac": phases["X_read_only"]["frac_of_8TBps"], "E_ms": phases["E_entropy_encode"]["ms"]}
         if other:   # the other BASELINE configs in short (value, dominant kernel, its roofline fraction): what a tail of the line keeps of them
@@ -534,12 +592,12 @@ def main():
             "host": {"nproc": os.cpu_count(), "cpu": cpu_model()},
             "bytes": {"in": int(t.in_bytes), "out": int(t.out_bytes), "coef_one_way": int(t.coef_bytes)},
             "metric": "megapixels/sec JPEG q=80 1920x1080 batch", "value": round(value, 1), "unit": "MP/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
+            "steps": args.steps, "warmup": args.warmup, "full": args.full, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "int32", "data": "synthetic",
             "config": {"workload": "configs[1]: synthetic 1920x1080 q92 4:2:0 baseline JPEGs -> -q 80 progressive, inputs resident in HBM",
                        "files_per_gpu_per_step": args.batch, "unique_images": nuniq, "sharding": f"files/{world} ranks, no collective",
                        "profile": profile},
-            "parity_spot_check": bool(parity), "parity_files_checked": len(all_idx),
+            "parity_spot_check": parity, "parity_files_checked": len(all_idx),   # (None: a plain run checks nothing, --full does)
             "device_ms_per_step": round(sum(tm.total_ms for tm in timings) / len(timings), 3),
             "cpu_baseline": cpu, "roofline": roof, "phases": phases, "summary": summary,
         }
@@ -550,7 +608,7 @@ def main():
 
 
 def boundary_strong_leg(api, pkg, args, rank, world, local, barrier, reduce_max_sum):
-    """the host-bound STRONG-scaling number inside the default invocation (so that a 1/2/4/8-GPU sweep of `bench.py --gpus N` carries it next to the
+    """the host-bound STRONG-scaling number inside a --full invocation (so that a 1/2/4/8-GPU sweep of `bench.py --gpus N --full` carries it next to the
     resident weak-scaling value): one shared list of --boundary-total 1080p files (every rank makes the same list), rank r takes files r, r + N, ...
     (caesium-clt_amd/sharding.py) and calls cs_batch_compress on them from host buffers on its own device -- marker parse on the host's cores, pinned
     upload, kernels, download all inside the time; value = all files / the slowest rank's seconds.  No collective on the data path."""

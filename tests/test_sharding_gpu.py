@@ -28,7 +28,7 @@ def test_two_ranks_share_one_list_at_the_boundary():
 
 
 def test_the_default_invocations_scaling_legs_run_on_one_device(monkeypatch):
-    """the records `bench.py --gpus N` adds beside the resident number (round 5): the strong-scaling boundary leg (here with one rank) and rank 0's
+    """the records `bench.py --gpus N --full` adds beside the resident number (round 5): the strong-scaling boundary leg (here with one rank) and rank 0's
     `caesiumclt --gpus N` over the shared list -- N = 2 device slots on the one GPU of this box (CSH_CLI_SAME_DEVICE), so that the code a multi-GPU
     sweep runs has run before the sweep does"""
     import argparse

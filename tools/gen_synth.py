@@ -33,15 +33,69 @@ def synth_rgb(i, w=1920, h=1080, texture=0.0):
     return np.clip(img, 0, 255).astype(np.uint8)
 
 
-def synth_jpeg(i, w=1920, h=1080, quality=92, subsampling=2, progressive=False, optimize=False, restart_rows=0, texture=0.0):
-    """Source JPEG as config 2 uses: Pillow/libjpeg-turbo, q92, 4:2:0, baseline, no optimise."""
+def synth_rgb_fast(i, w=1920, h=1080):
+    """synth_rgb(i, w, h) bit for bit (texture 0), in about a quarter of its time: the same draws from the same generator, the
+    sinusoids summed in float32 from arguments reduced modulo 2 pi per row and per column (within ~1e-4 of synth_rgb's float64
+    sums), and every sample that lands within 1/256 of a whole number -- where the truncation to u8 could go the other way --
+    recomputed with synth_rgb's own float64 expressions before the rectangles are painted."""
+    rng = np.random.Generator(np.random.PCG64(0xCAE50000 + i))
+    noise = rng.normal(0.0, 6.0, (h, w)).astype(np.float32)
+    x = np.arange(w, dtype=np.float32)   # the values of synth_rgb's xx / yy
+    y = np.arange(h, dtype=np.float32)
+    planes = np.empty((3, h, w), dtype=np.float32)
+    tmp = np.empty((h, w), dtype=np.float32)
+    for c in range(3):
+        base = rng.uniform(40, 200)
+        sx, sy = rng.uniform(-0.05, 0.05, 2)
+        ch = planes[c]
+        np.add((base + sx * x).astype(np.float32)[None, :], (sy * y).astype(np.float32)[:, None], out=ch)
+        waves = []
+        for _ in range(6):
+            fx, fy = rng.uniform(0.002, 0.08, 2)
+            ph = rng.uniform(0, 2 * np.pi)
+            amp = rng.uniform(5, 40)
+            waves.append((fx, fy, ph, amp))
+            np.add(np.remainder(fy * y + ph, 2 * np.pi).astype(np.float32)[:, None],
+                   np.remainder(fx * x, 2 * np.pi).astype(np.float32)[None, :], out=tmp)
+            np.sin(tmp, out=tmp)
+            tmp *= np.float32(amp)
+            ch += tmp
+        ch += noise
+        np.rint(ch, out=tmp)
+        tmp -= ch
+        np.abs(tmp, out=tmp)
+        k = np.flatnonzero(tmp < 1.0 / 256)
+        xs, ys = (k % w).astype(np.float32), (k // w).astype(np.float32)
+        exact = base + sx * xs + sy * ys
+        for fx, fy, ph, amp in waves:
+            exact = exact + amp * np.sin(fx * xs + fy * ys + ph)
+        ch.reshape(-1)[k] = exact + noise.reshape(-1)[k]
+    for _ in range(8):
+        rw = int(rng.integers(40, 401)); rh = int(rng.integers(40, 301))
+        rw = min(rw, w); rh = min(rh, h)
+        x0 = int(rng.integers(0, max(1, w - rw + 1))); y0 = int(rng.integers(0, max(1, h - rh + 1)))
+        planes[:, y0:y0 + rh, x0:x0 + rw] = rng.uniform(0, 255, 3).astype(np.float32)[:, None, None]
+    np.clip(planes, 0, 255, out=planes)
+    img = np.empty((h, w, 3), dtype=np.uint8)
+    np.copyto(img.transpose(2, 0, 1), planes, casting="unsafe")
+    return img
+
+
+def synth_jpeg(i, w=1920, h=1080, quality=92, subsampling=2, progressive=False, optimize=False, restart_rows=0, texture=0.0, fast=False):
+    """Source JPEG as config 2 uses: Pillow/libjpeg-turbo, q92, 4:2:0, baseline, no optimise.  fast: the pixels from
+    synth_rgb_fast (the same file, texture 0 only)."""
     from PIL import Image
     b = io.BytesIO()
     kw = {}
     if restart_rows:
         kw["restart_marker_rows"] = restart_rows
-    Image.fromarray(synth_rgb(i, w, h, texture), "RGB").save(b, format="JPEG", quality=quality, subsampling=subsampling,
-                                                    progressive=progressive, optimize=optimize, **kw)
+    if fast:
+        assert not texture, "synth_rgb_fast draws no texture"
+        rgb = synth_rgb_fast(i, w, h)
+    else:
+        rgb = synth_rgb(i, w, h, texture)
+    Image.fromarray(rgb, "RGB").save(b, format="JPEG", quality=quality, subsampling=subsampling,
+                                     progressive=progressive, optimize=optimize, **kw)
     return b.getvalue()
 
 
