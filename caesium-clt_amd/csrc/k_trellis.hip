@@ -19,6 +19,9 @@
 //                  (81 transitions per block, all in registers), back-pointers in a side array, the path written back.
 // All cost arithmetic is float in mozjpeg's order of operations (no contraction: the Makefile passes -ffp-contract=off); lambda is
 // double arithmetic rounded once, as in the C source.  No MFMA: the programme is a data-dependent minimisation, not a contraction.
+#include <algorithm>
+#include <atomic>
+#include <cassert>
 #include <utility>
 
 #include "kernels.h"
@@ -28,8 +31,8 @@ namespace csh {
 #define CSH_TR_CAP 16                      // list entries per block that live in LDS (192 bytes per block)
 #define CSH_TR_WGU uint32_t(CSH_TR_WG)     // blocks (= lanes) per workgroup of the AC kernel: kernels.h
 #define CSH_TR_SPILL (63 - CSH_TR_CAP)     // the rest, in HBM
-#define CSH_TR_MAXWG 2048                  // workgroups of the AC kernel (each loops over its share of the chunks)
-size_t trellis_spill_words() { return size_t(CSH_TR_MAXWG) * CSH_TR_SPILL * 3u * CSH_TR_WGU; }
+#define CSH_TR_MAXWG 2048                  // most workgroups of the AC kernel, whatever the device answers (the spill area is sized from the grid)
+size_t trellis_spill_words(uint32_t nslots) { return size_t(nslots) * CSH_TR_SPILL * 3u * CSH_TR_WGU; }
 
 #ifdef CSH_EMUL
 #define CSH_ANY(p) (p)                     // a lane cannot see the others there: its own loop bounds
@@ -101,8 +104,8 @@ struct TrLds {
 
 // tables of the chunk's component -> LDS (all 256 lanes)
 // (the sweep reads the quantiser's three values per position from here: as loads from HBM they were 189 dependent round trips per wave)
-__device__ __forceinline__ static void trellis_stage(const TrellisCtx &c, uint32_t chi, float *s_lenf, float *s_runf, int *s_eob, int32_t *s_q8, uint32_t *s_qmul, uint32_t *s_qsh, float *s_lt, float *s_rcp) {
-    const TrellisWork &w = c.work[c.chunks[chi].work];
+__device__ __forceinline__ static void trellis_stage(const TrellisCtx &c, uint32_t wi, float *s_lenf, float *s_runf, int *s_eob, int32_t *s_q8, uint32_t *s_qmul, uint32_t *s_qsh, float *s_lt, float *s_rcp) {
+    const TrellisWork &w = c.work[wi];
     const ImgDesc &im = c.imgs[w.image];
     const DevQuant &Q = c.quant[im.qt_out[w.comp]];
     const int tid = int(threadIdx.x);
@@ -118,13 +121,13 @@ __device__ __forceinline__ static void trellis_stage(const TrellisCtx &c, uint32
     if (tid < 64) { s_q8[tid] = Q.div[tid]; s_qmul[tid] = Q.mul[tid]; s_qsh[tid] = Q.sh[tid]; s_lt[tid] = Q.lt[tid]; s_rcp[tid] = Q.rcp[tid]; }
 }
 
-__device__ __forceinline__ static void trellis_block(const TrellisCtx &c, uint32_t chi, uint32_t wg_slot, const TrLds &L) {
-    const TrellisChunk ch = c.chunks[chi];
-    const TrellisWork &w = c.work[ch.work];
+// chunk j of work item wi: its blocks j * 256 .. j * 256 + 255 (in the order of c.perm), one per lane
+__device__ __forceinline__ static void trellis_block(const TrellisCtx &c, uint32_t wi, uint32_t j, uint32_t wg_slot, const TrLds &L) {
+    const TrellisWork &w = c.work[wi];
     const ImgDesc &im = c.imgs[w.image];
     const CompGeom g = im.out[w.comp];
     const int tid = int(threadIdx.x);
-    const uint32_t slot = ch.j * CSH_TR_WGU + uint32_t(tid);
+    const uint32_t slot = j * CSH_TR_WGU + uint32_t(tid);
     if (slot >= w.nunits) return;
     const uint32_t u = c.perm ? c.perm[w.unit_base + slot] : slot;   // the blocks of a chunk: neighbours in the order of list length (k_trellis_sort), or in raster order
     const int by = int(u) / g.real_bw, b = by * g.bw + (int(u) - by * g.real_bw);
@@ -378,17 +381,28 @@ __global__ void __launch_bounds__(CSH_TR_WG) k_trellis_ac(TrellisCtx c) {
     CSH_SHARED float s_rcp[64];
     TrLds L; L.A = s_A; L.Z = s_Z; L.P = s_P; L.lenf = s_lenf; L.runf = s_runf; L.q8 = s_q8; L.qmul = s_qmul; L.qsh = s_qsh; L.lt = s_lt; L.rcp = s_rcp;
 #ifdef CSH_EMUL
+    // one workgroup per run (no queue: the emulation has no real barrier to hand a run to a persistent workgroup with), one spill slot
     CSH_PHASE_LOOP(2) {
-        if (phase == 0) { trellis_stage(c, blockIdx.x, s_lenf, s_runf, &s_eob, s_q8, s_qmul, s_qsh, s_lt, s_rcp); continue; }
+        const TrellisRun rn = c.runs[blockIdx.x];
+        if (phase == 0) { trellis_stage(c, rn.work, s_lenf, s_runf, &s_eob, s_q8, s_qmul, s_qsh, s_lt, s_rcp); continue; }
         L.lenEOB = s_eob;
-        trellis_block(c, blockIdx.x, 0u, L);
+        for (uint32_t j = rn.j; j < rn.j + rn.n; j++) trellis_block(c, rn.work, j, 0u, L);
     }
 #else
-    for (uint32_t chi = blockIdx.x; chi < c.nchunks; chi += gridDim.x) {
-        trellis_stage(c, chi, s_lenf, s_runf, &s_eob, s_q8, s_qmul, s_qsh, s_lt, s_rcp);
+    // persistent workgroups (as many as are resident at once: launch_trellis_ac) take runs from the queue, densest first, until it is
+    // empty.  A run's chunks share the work item's tables: one staging and three barriers per run.  Between the chunks of a run no
+    // barrier: the lists are per lane and the tables are only read, so the four waves go through the run each at its own pace
+    CSH_SHARED uint32_t s_run;
+    for (;;) {
+        if (threadIdx.x == 0) s_run = atomicAdd(c.queue, 1u);
+        __syncthreads();
+        const uint32_t ri = s_run;   // (written again only behind the barrier at the end of the run)
+        if (ri >= c.nruns) break;
+        const TrellisRun rn = c.runs[ri];
+        trellis_stage(c, rn.work, s_lenf, s_runf, &s_eob, s_q8, s_qmul, s_qsh, s_lt, s_rcp);
         __syncthreads();
         L.lenEOB = s_eob;
-        trellis_block(c, chi, blockIdx.x, L);
+        for (uint32_t j = rn.j; j < rn.j + rn.n; j++) trellis_block(c, rn.work, j, blockIdx.x, L);
         __syncthreads();
     }
 #endif
@@ -418,6 +432,7 @@ __global__ void __launch_bounds__(64) k_trellis_dc(TrellisCtx c) {
     CSH_SHARED float s_costs[64][13];   // (a column per lane: the lanes of a wave belong to different components now)
     float *s_cost = s_costs[threadIdx.x & 63u];
     for (int i = 0; i < 12; i++) s_cost[i] = float(i + int(w.table_dc < 0 ? kStdDcLen[w.comp ? 1 : 0][i] : c.tables[w.table_dc].size[i]));
+    s_cost[12] = __builtin_inff();   // a difference no two real levels make (they stay within 11 bits): only the closed form's pairs with a level past ncand, infinite anyway, read it
     const int q = Q.div[0];
     const uint32_t qmul = Q.mul[0], qsh = Q.sh[0];
     const float lt0 = Q.lt[0];
@@ -455,7 +470,7 @@ __global__ void __launch_bounds__(64) k_trellis_dc(TrellisCtx c) {
                 int cand = qval - half + k;
                 cand = cand > TRELLIS_MAX_LEVEL ? TRELLIS_MAX_LEVEL : cand;
                 cand = cand < -TRELLIS_MAX_LEVEL ? -TRELLIS_MAX_LEVEL : cand;
-                const int delta = cand * q - x;
+                const int delta = k < ncand ? cand * q - x : 0;   // (chosen before the square: a level past ncand may be far enough off to overflow it)
                 dist[k] = k < ncand ? float(delta * delta) * lambda_dc : __builtin_inff();
                 ccur[k] = sgn ? -cand : cand;
             }
@@ -524,12 +539,38 @@ __global__ void __launch_bounds__(64) k_trellis_dc(TrellisCtx c) {
     }
 }
 
-void launch_trellis_ac(hipStream_t st, const TrellisCtx &c) {
-    if (!c.nchunks) return;
 #ifdef CSH_EMUL
-    CSH_LAUNCH_PHASED(k_trellis_ac, 2, dim3(c.nchunks), dim3(CSH_TR_WG), st, c);
+uint32_t trellis_ac_slots() { return 1u; }   // the workgroups run one after another
 #else
-    CSH_LAUNCH(k_trellis_ac, dim3(c.nchunks < CSH_TR_MAXWG ? c.nchunks : CSH_TR_MAXWG), dim3(CSH_TR_WG), st, c);
+// resident workgroups per CU (the occupancy query) x CUs, once per device: a larger grid only queues workgroups behind the first ones,
+// and its spill area is never touched all at once
+uint32_t trellis_ac_slots() {
+    static std::atomic<uint32_t> cached[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    dev &= 63;
+    uint32_t n = cached[dev].load(std::memory_order_relaxed);
+    if (n) return n;
+    int per_cu = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_trellis_ac, CSH_TR_WG, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 1;
+    n = uint32_t(per_cu) * uint32_t(cus);
+    n = n < CSH_TR_MAXWG ? n : CSH_TR_MAXWG;
+    cached[dev].store(n, std::memory_order_relaxed);
+    return n;
+}
+#endif
+
+void launch_trellis_ac(hipStream_t st, const TrellisCtx &c) {
+    if (!c.nruns || !c.nslots) return;
+#ifdef CSH_EMUL
+    assert(c.nslots >= 1u);   // every workgroup on spill slot 0
+    CSH_LAUNCH_PHASED(k_trellis_ac, 2, dim3(c.nruns), dim3(CSH_TR_WG), st, c);
+#else
+    // the queue was zeroed on the stream in front of this launch (TrellisCtx::queue); the grid is what is resident at once, never more
+    // workgroups than the spill area has slots for
+    const uint32_t nwg = std::min(std::min(c.nruns, c.nslots), trellis_ac_slots());
+    CSH_LAUNCH(k_trellis_ac, dim3(nwg), dim3(CSH_TR_WG), st, c);
 #endif
 }
 void launch_trellis_dc(hipStream_t st, const TrellisCtx &c) {

@@ -149,22 +149,27 @@ void launch_reset_works(hipStream_t st, ScanWork *work, int nwork);
 // ---- mozjpeg's trellis quantiser (k_trellis.hip): re-quantise every block from the retained DCT with the statistics pass's code
 // lengths as rates -- AC coefficients per block (k_trellis_ac), DC coefficients along each row of blocks (k_trellis_dc)
 #ifndef CSH_TR_WG
-#define CSH_TR_WG 256   // blocks per workgroup (and per TrellisChunk) of k_trellis_ac (64 -- no wave waits for another's densest block, but the tables are staged four times as often -- measured 6 % slower)
+#define CSH_TR_WG 256   // blocks per workgroup (and per chunk) of k_trellis_ac (64 -- no wave waits for another's densest block, but the tables are staged four times as often -- measured 6 % slower)
+#endif
+#ifndef CSH_TR_RUN
+#define CSH_TR_RUN 8    // chunks per TrellisRun at most (the sweep over 4, 8 and 16)
 #endif
 struct TrellisCtx {
     const ImgDesc *imgs;
     const DevQuant *quant;
     const TrellisWork *work;
     int nwork;
-    const TrellisChunk *chunks;
-    uint32_t nchunks;
+    const TrellisRun *runs;    // densest first: every work item's first run, then every second one, ..
+    uint32_t nruns;
+    uint32_t *queue;           // [1] the next run to hand out (zeroed in front of every launch; the emulation build takes one workgroup per run instead)
+    uint32_t nslots;           // workgroups the spill area has room for: the grid never exceeds it
     const DevEncTable *tables;
     const int16_t *raw;        // unquantised jfdctint output, tiles (index relative to raw_tile0)
     uint32_t raw_tile0;
     int16_t *coef;             // re-quantised coefficients (tiles)
     uint64_t *dcrec;           // per real block: lambda (float bits) << 32 | the unquantised DC & 0xFFFF (AC kernel -> DC kernel)
     uint64_t *dcbt;            // per real block: back-pointers of the DC path (9 x 4 bits) | rounded DC level << 36 | sign << 47
-    uint32_t *spill;           // per workgroup of the AC kernel: entries of the block lists that do not fit LDS
+    uint32_t *spill;           // per workgroup of the AC kernel (slot = blockIdx.x, never shared): entries of the block lists that do not fit LDS
     uint32_t max_rows;         // DC kernel: most iMCU rows of a component
     const uint8_t *blk_cnt;    // per real block (unit_base + u): non-zero scalar levels, the length of its list (the builder of the statistics lists counted them); null: no sorting
     uint32_t *perm;            // per work item, unit_base + slot -> block: the blocks in order of list length (k_trellis_sort), so that the 256 blocks of a chunk -- the 64 of a wave -- run equally long programmes
@@ -183,7 +188,8 @@ struct TrellisCtx {
 void launch_trellis_sort(hipStream_t st, const TrellisCtx &c);   // fills TrellisCtx::perm from ::blk_cnt
 void launch_trellis_ac(hipStream_t st, const TrellisCtx &c);
 void launch_trellis_dc(hipStream_t st, const TrellisCtx &c);
-size_t trellis_spill_words();   // size of TrellisCtx::spill in u32
+uint32_t trellis_ac_slots();       // workgroups of k_trellis_ac that fit the current device at once (asked once per device)
+size_t trellis_spill_words(uint32_t nslots);   // size of TrellisCtx::spill in u32 for that many workgroups
 
 // generic device primitive: out[i] = sum_{j<i} in[j] for i in [0, n]  (n+1 outputs; in[] has n entries)
 void launch_exclusive_scan(hipStream_t st, const uint32_t *in, uint64_t *out, uint64_t n, void *tmp, size_t tmp_bytes);

@@ -162,7 +162,7 @@ struct csh_batch {
     bool trellis = false, dering = false;
     Stage tstage;
     std::vector<TrellisWork> twork;
-    std::vector<TrellisChunk> tchunks;
+    std::vector<TrellisRun> truns;        // k_trellis_ac's queue: runs of up to CSH_TR_RUN chunks, every work item's first run, then every second one, ..
     uint32_t t_units = 0, t_max_rows = 0;
     std::vector<uint32_t> trows;          // k_trellis_dc: (work item << 16 | iMCU row), longest rows first
     bool t_sort = false;                  // k_trellis_ac takes its blocks in order of list length (progressive output: the statistics lists count them)
@@ -226,7 +226,8 @@ struct csh_batch {
     DevBuf<NzChunk> d_nzchunks;
     DevBuf<uint32_t> d_nz_pool, d_nz_cursor, d_nz_chunk_off, d_nz_chunk_cnt, d_list_slots, d_tok_slots;
     DevBuf<TrellisWork> d_twork;
-    DevBuf<TrellisChunk> d_tchunks;
+    DevBuf<TrellisRun> d_truns;
+    DevBuf<uint32_t> d_tqueue;
     DevBuf<uint32_t> d_trows, d_tperm;
     DevBuf<uint8_t> d_tblk_cnt;
     DevBuf<uint16_t> d_tblk_off;
@@ -1253,7 +1254,6 @@ static int batch_create(const CByteArray *inputs, size_t count, const CCSParamet
                 tw.table_dc = progressive ? -1 : int32_t(sw.table_base);
                 tw.nunits = sw.nunits; tw.unit_base = b->t_units;
                 b->t_units += sw.nunits;
-                for (uint32_t j = 0; j < (sw.nunits + CSH_TR_WG - 1) / CSH_TR_WG; j++) b->tchunks.push_back(TrellisChunk{uint32_t(b->twork.size()), j});
                 b->t_max_rows = std::max<uint32_t>(b->t_max_rows, uint32_t((im.out[c].real_bh + im.out[c].v - 1) / im.out[c].v));
                 tw.nzset = 0xFFFFFFFFu;
                 if (progressive) {
@@ -1265,6 +1265,15 @@ static int batch_create(const CByteArray *inputs, size_t count, const CCSParamet
             }
         }
         b->stage_end(tg);
+        {   // the AC kernel's runs, j-major: the chunks at the front of a work item hold its longest lists (k_trellis_sort), so the queue
+            // hands out the heavy chunks of every component first and ends on light ones
+            std::vector<uint32_t> nch(b->twork.size());
+            uint32_t most = 0;
+            for (size_t wi = 0; wi < b->twork.size(); wi++) { nch[wi] = (b->twork[wi].nunits + CSH_TR_WG - 1) / CSH_TR_WG; most = std::max(most, nch[wi]); }
+            for (uint32_t j = 0; j < most; j += CSH_TR_RUN)
+                for (size_t wi = 0; wi < b->twork.size(); wi++)
+                    if (j < nch[wi]) b->truns.push_back(TrellisRun{uint32_t(wi), j, std::min<uint32_t>(CSH_TR_RUN, nch[wi] - j)});
+        }
         {   // the DC walks, longest first (a wave's 64 lanes then walk rows of a length)
             const char *ts = getenv("CSH_TR_SORT");
             b->t_sort = progressive && !(ts && !strcmp(ts, "0"));
@@ -1348,8 +1357,8 @@ static int batch_create(const CByteArray *inputs, size_t count, const CCSParamet
             hipMemsetAsync(b->d_slot_work.p, 0, (size_t(b->nslots) + 1) * sizeof(uint32_t), st) != hipSuccess) { csh_set_error("hipMemsetAsync failed"); return CS_ERR_NO_DEVICE; }
         launch_make_slots(st, b->d_swork.p, uint32_t(b->swork.size()), b->d_script.p, b->d_nzlists.p, b->d_slots.p, b->d_slot_work.p, b->d_list_slots.p, b->d_tok_slots.p);
         if (b->trellis && (b->d_trows.upload(b->trows, st) || (b->t_sort && (b->d_tperm.alloc(size_t(b->t_units) + 1) || b->d_tblk_cnt.alloc(size_t(b->t_units) + 1) || (b->nz_once && b->d_tblk_off.alloc(size_t(b->t_units) + 1)))))) return CS_ERR_NO_DEVICE;
-        if (b->trellis && (b->d_twork.upload(b->twork, st) || b->d_tchunks.upload(b->tchunks, st) || b->d_tlambda.alloc(size_t(b->t_units) + 1) || b->d_tdcbt.alloc(size_t(b->t_units) + 1) ||
-                           b->d_tspill.alloc(trellis_spill_words()) || b->d_dct_raw.alloc(size_t(b->ntiles_out) * CSH_TILE_I16)))
+        if (b->trellis && (b->d_twork.upload(b->twork, st) || b->d_truns.upload(b->truns, st) || b->d_tqueue.alloc(1) || b->d_tlambda.alloc(size_t(b->t_units) + 1) || b->d_tdcbt.alloc(size_t(b->t_units) + 1) ||
+                           b->d_tspill.alloc(trellis_spill_words(trellis_ac_slots())) || b->d_dct_raw.alloc(size_t(b->ntiles_out) * CSH_TILE_I16)))
             return CS_ERR_NO_DEVICE;
         for (size_t n = 0; px && n < count; n++) {
             const Item &it = b->items[n];
@@ -1842,9 +1851,11 @@ static int run_once(csh_batch *b, csh_timing *t, bool requant_only) {
         MARK();
         TrellisCtx tc;
         memset(&tc, 0, sizeof tc);
-        tc.imgs = b->d_imgs.p; tc.quant = b->d_quants.p; tc.work = b->d_twork.p; tc.nwork = int(b->twork.size()); tc.chunks = b->d_tchunks.p; tc.nchunks = uint32_t(b->tchunks.size());
+        tc.imgs = b->d_imgs.p; tc.quant = b->d_quants.p; tc.work = b->d_twork.p; tc.nwork = int(b->twork.size()); tc.runs = b->d_truns.p; tc.nruns = uint32_t(b->truns.size());
         tc.tables = b->d_tables.p; tc.raw = b->d_dct_raw.p; tc.raw_tile0 = b->ntiles_in; tc.coef = b->d_coef.p; tc.dcrec = b->d_tlambda.p; tc.dcbt = b->d_tdcbt.p;
-        tc.spill = b->d_tspill.p; tc.max_rows = b->t_max_rows;
+        tc.spill = b->d_tspill.p; tc.nslots = uint32_t(b->d_tspill.n / trellis_spill_words(1)); tc.max_rows = b->t_max_rows;
+        tc.queue = b->d_tqueue.p;
+        if (b->d_tqueue.zero(st)) return -1;   // every run of the batch (size targeting, repeated runs) starts the queue at its head
         tc.rows = b->d_trows.p; tc.nrows = uint32_t(b->trows.size());
         if (b->t_sort) { tc.blk_cnt = b->d_tblk_cnt.p; tc.perm = b->d_tperm.p; }
         if (b->t_sort && b->nz_once) {

@@ -261,7 +261,7 @@ struct SlotRec {
 };
 
 // mozjpeg's trellis quantiser (k_trellis.hip; CSH_PROFILE=mozjpeg): one work item per (image, component) -- the component's statistics
-// scan (a ScanWork of the trellis stage) supplies the rate tables -- and one chunk of the AC kernel per 256 of its blocks
+// scan (a ScanWork of the trellis stage) supplies the rate tables -- and one chunk of the AC kernel per 256 of its blocks, handed out in runs
 struct TrellisWork {
     int image, comp;
     uint32_t table_ac;       // DevEncTable of the statistics pass: code lengths of the AC symbols
@@ -271,7 +271,8 @@ struct TrellisWork {
     uint32_t nzset;          // the component's NzSet (its level-0 list takes the chosen levels: TrellisCtx::nz_pool), 0xFFFFFFFF: none
     uint32_t pad[1];
 };
-struct TrellisChunk { uint32_t work, j; };
+// what one grab of k_trellis_ac's queue hands a workgroup: chunks j .. j + n - 1 of a work item (one staging of its tables for all n)
+struct TrellisRun { uint32_t work, j, n; };
 
 // encoder-side Huffman table as generated on the device
 struct DevEncTable {
