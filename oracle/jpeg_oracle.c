@@ -686,7 +686,8 @@ static void make_dummy_blocks(cso_image *im, int ci) {
             for (int x = 0; x < k->h; x++) { int16_t *o = k->coef + ((size_t)by * k->bw + m * k->h + x) * 64; memset(o, 0, 128); o[0] = last; }
         }
 }
-static void forward_component(const uint8_t *full, int W, int H, cso_image *im, int ci, int deringing, int16_t *raw /* unquantised DCT per padded block, or NULL */) {
+static void forward_component(const uint8_t *full, int W, int H, cso_image *im, int ci, int deringing, int16_t *raw /* unquantised DCT per padded block, or NULL */,
+                              uint8_t *samples /* the DCT's input samples per padded block (in front of deringing), or NULL */) {
     cso_comp *k = &im->comp[ci];
     int hx = im->hmax / k->h, vx = im->vmax / k->v;
     int pw = k->real_bw * 8, ph = k->bh * 8;         /* sample plane fed to the DCT */
@@ -723,6 +724,7 @@ static void forward_component(const uint8_t *full, int W, int H, cso_image *im, 
     for (int by = 0; by < k->real_bh; by++) {
         for (int bx = 0; bx < k->real_bw; bx++) {
             for (int y = 0; y < 8; y++) for (int x = 0; x < 8; x++) s[8 * y + x] = (int32_t)pl[(size_t)(by * 8 + y) * pw + bx * 8 + x] - 128;
+            if (samples) for (int i = 0; i < 64; i++) samples[((size_t)by * k->bw + bx) * 64 + i] = (uint8_t)(s[i] + 128);
             if (deringing) cso_dering_block(s, qt[0]);
             fdct_islow_ls(s, d);
             int16_t *o = k->coef + ((size_t)by * k->bw + bx) * 64;
@@ -739,8 +741,9 @@ static void forward_component(const uint8_t *full, int W, int H, cso_image *im, 
     free(pl);
 }
 
-static void trellis_image(cso_image *im, int16_t *const raw[], const cso_enc_params *p);
-int cso_forward(const uint8_t *pix, int w, int h, int ncomp, const cso_enc_params *p, const uint16_t *qto, cso_image **out) {
+static void trellis_image(cso_image *im, int16_t *const raw[], const cso_enc_params *p, cso_trellis_inputs_t *cap);
+/* cso_forward with an optional capture of what the quantiser sees (cso_trellis_inputs); cap == NULL is cso_forward */
+static int forward_capture(const uint8_t *pix, int w, int h, int ncomp, const cso_enc_params *p, const uint16_t *qto, cso_image **out, cso_trellis_inputs_t *cap) {
     *out = NULL;
     if (ncomp != 1 && ncomp != 3) FAIL("forward: only 1 or 3 components");
     cso_image *im = (cso_image *)calloc(1, sizeof *im);
@@ -761,13 +764,23 @@ int cso_forward(const uint8_t *pix, int w, int h, int ncomp, const cso_enc_param
     int16_t *raw[CSO_MAX_COMPS] = {0};
     for (int c = 0; c < ncomp; c++) {
         for (size_t i = 0; i < (size_t)w * h; i++) full[i] = pix[i * ncomp + c];
-        if (p->trellis) raw[c] = (int16_t *)calloc((size_t)im->comp[c].bw * im->comp[c].bh * 64, sizeof(int16_t));
-        forward_component(full, w, h, im, c, p->deringing, raw[c]);
+        const size_t nb = (size_t)im->comp[c].bw * im->comp[c].bh * 64;
+        if (p->trellis || cap) raw[c] = (int16_t *)calloc(nb, sizeof(int16_t));
+        if (cap) cap->samples[c] = (uint8_t *)calloc(nb, 1);
+        forward_component(full, w, h, im, c, p->deringing, raw[c], cap ? cap->samples[c] : NULL);
     }
     free(full);
-    if (p->trellis) { trellis_image(im, raw, p); for (int c = 0; c < ncomp; c++) free(raw[c]); }
+    if (p->trellis) trellis_image(im, raw, p, cap);
+    else if (cap) for (int c = 0; c < ncomp; c++) cso_trellis_tables(im, c, cap->aclen[c], cap->dclen[c]);
+    for (int c = 0; c < ncomp; c++) {
+        if (cap) { cap->raw[c] = raw[c]; continue; }
+        free(raw[c]);
+    }
     *out = im;
     return 0;
+}
+int cso_forward(const uint8_t *pix, int w, int h, int ncomp, const cso_enc_params *p, const uint16_t *qto, cso_image **out) {
+    return forward_capture(pix, w, h, ncomp, p, qto, out, NULL);
 }
 
 /* ------------------------------------------------------------------------------------------ */
@@ -1100,12 +1113,13 @@ void cso_trellis_tables(const cso_image *im, int ci, uint8_t aclen[256], uint8_t
     if (im->progressive) memcpy(dclen, STD_DC_LEN[id], 12);
     else { uint8_t l[256]; optimal_lengths(freq[id], l); memcpy(dclen, l, 17); }
 }
-static void trellis_image(cso_image *im, int16_t *const raw[], const cso_enc_params *p) {
+static void trellis_image(cso_image *im, int16_t *const raw[], const cso_enc_params *p, cso_trellis_inputs_t *cap) {
     (void)p;
     for (int ci = 0; ci < im->ncomp; ci++) {
         cso_comp *k = &im->comp[ci];
         uint8_t aclen[256], dclen[17];
         cso_trellis_tables(im, ci, aclen, dclen);
+        if (cap) { memcpy(cap->aclen[ci], aclen, 256); memcpy(cap->dclen[ci], dclen, 17); }
         int16_t last_dc = 0;
         for (int by = 0; by < k->real_bh; by++) {
             if (by % k->v == 0) last_dc = 0;   /* compress_trellis_pass: the predictor starts at 0 in every iMCU row */
@@ -1373,19 +1387,18 @@ int cso_search_script(const cso_image *im, const cso_enc_params *p, cso_scan *ou
     return cso_search_progression(&hdr, p, out);
 }
 
+static int decode_resize_forward(const cso_image *src, const cso_enc_params *p, int resize, int width, int height, cso_image **dst, cso_trellis_inputs_t *cap);
 int cso_jpeg_compress(const uint8_t *in, size_t n, const cso_enc_params *p, int lossless, uint8_t **out, size_t *out_len) {
     cso_image *src = NULL, *dst = NULL;
     if (cso_decode(in, n, &src)) return -1;
     int rc = -1;
     if (lossless) { rc = cso_encode(src, p, NULL, 0, out, out_len); cso_image_free(src); return rc; }
-    if (src->ncomp != 1 && src->ncomp != 3) { cso_image_free(src); FAIL("unsupported component count %d", src->ncomp); }
-    uint8_t *pix = (uint8_t *)malloc((size_t)src->width * src->height * src->ncomp);
-    if (cso_decode_pixels(src, pix) == 0 && cso_forward(pix, src->width, src->height, src->ncomp, p, NULL, &dst) == 0) {
+    if (decode_resize_forward(src, p, 0, 0, 0, &dst, NULL) == 0) {
         dst->meta = src->meta; dst->meta_len = src->meta_len;
         rc = cso_encode(dst, p, NULL, 0, out, out_len);
         dst->meta = NULL; dst->meta_len = 0;
     }
-    free(pix); cso_image_free(src); cso_image_free(dst);
+    cso_image_free(src); cso_image_free(dst);
     return rc;
 }
 
@@ -1503,23 +1516,56 @@ int cso_pixels_to_jpeg(const uint8_t *pix, int W, int H, int nc, const cso_enc_p
     free(rs); cso_image_free(dst);
     return rc;
 }
+/* the lossy half of cso_jpeg_compress (resize 0) and of cso_jpeg_compress_resized (resize 1): decoded pixels -> (YCbCr -> RGB -> Lanczos3 ->
+   YCbCr) -> forward path; cap != NULL also keeps what the quantiser saw (cso_trellis_inputs) */
+static int decode_resize_forward(const cso_image *src, const cso_enc_params *p, int resize, int width, int height, cso_image **dst, cso_trellis_inputs_t *cap) {
+    *dst = NULL;
+    if (src->ncomp != 1 && src->ncomp != 3) FAIL("unsupported component count %d", src->ncomp);
+    int W = src->width, H = src->height, nc = src->ncomp, nw = W, nh = H, rc = -1;
+    if (resize) cso_compute_dimensions(W, H, width, height, &nw, &nh);
+    uint8_t *pix = (uint8_t *)malloc((size_t)W * H * nc), *rs = resize ? (uint8_t *)malloc((size_t)nw * nh * nc) : pix;
+    if (cso_decode_pixels(src, pix) == 0) {
+        if (resize) {
+            if (nc == 3) cso_ycc_to_rgb(pix, (size_t)W * H, pix);
+            cso_lanczos3_resize(pix, W, H, nc, nw, nh, rs);
+            if (nc == 3) cso_rgb_to_ycc(rs, (size_t)nw * nh, rs);
+        }
+        rc = forward_capture(rs, nw, nh, nc, p, NULL, dst, cap);
+    }
+    if (rs != pix) free(rs);
+    free(pix);
+    return rc;
+}
 int cso_jpeg_compress_resized(const uint8_t *in, size_t n, const cso_enc_params *p, int width, int height, uint8_t **out, size_t *out_len) {
     cso_image *src = NULL, *dst = NULL;
     if (cso_decode(in, n, &src)) return -1;
-    if (src->ncomp != 1 && src->ncomp != 3) { cso_image_free(src); FAIL("unsupported component count %d", src->ncomp); }
-    int W = src->width, H = src->height, nc = src->ncomp, nw, nh, rc = -1;
-    cso_compute_dimensions(W, H, width, height, &nw, &nh);
-    uint8_t *pix = (uint8_t *)malloc((size_t)W * H * nc), *rs = (uint8_t *)malloc((size_t)nw * nh * nc);
-    if (cso_decode_pixels(src, pix) == 0) {
-        if (nc == 3) cso_ycc_to_rgb(pix, (size_t)W * H, pix);
-        cso_lanczos3_resize(pix, W, H, nc, nw, nh, rs);
-        if (nc == 3) cso_rgb_to_ycc(rs, (size_t)nw * nh, rs);
-        if (cso_forward(rs, nw, nh, nc, p, NULL, &dst) == 0) {
-            dst->meta = src->meta; dst->meta_len = src->meta_len;
-            rc = cso_encode(dst, p, NULL, 0, out, out_len);
-            dst->meta = NULL; dst->meta_len = 0;
-        }
+    int rc = -1;
+    if (decode_resize_forward(src, p, 1, width, height, &dst, NULL) == 0) {
+        dst->meta = src->meta; dst->meta_len = src->meta_len;
+        rc = cso_encode(dst, p, NULL, 0, out, out_len);
+        dst->meta = NULL; dst->meta_len = 0;
     }
-    free(pix); free(rs); cso_image_free(src); cso_image_free(dst);
+    cso_image_free(src); cso_image_free(dst);
     return rc;
+}
+int cso_trellis_inputs(const uint8_t *in, size_t n, const cso_enc_params *p, int width, int height, cso_trellis_inputs_t *out) {
+    memset(out, 0, sizeof *out);
+    cso_image *src = NULL, *dst = NULL;
+    if (cso_decode(in, n, &src)) return -1;
+    int rc = decode_resize_forward(src, p, width || height, width, height, &dst, out);
+    cso_image_free(src);
+    if (rc) { cso_trellis_inputs_free(out); return rc; }
+    out->ncomp = dst->ncomp;
+    for (int c = 0; c < dst->ncomp; c++) {
+        const cso_comp *k = &dst->comp[c];
+        out->h[c] = k->h; out->v[c] = k->v; out->bw[c] = k->bw; out->bh[c] = k->bh; out->real_bw[c] = k->real_bw; out->real_bh[c] = k->real_bh;
+        memcpy(out->qt[c], dst->qt[k->tq], 128);
+        out->coef[c] = (int16_t *)malloc((size_t)k->bw * k->bh * 64 * sizeof(int16_t));
+        memcpy(out->coef[c], k->coef, (size_t)k->bw * k->bh * 64 * sizeof(int16_t));
+    }
+    cso_image_free(dst);
+    return 0;
+}
+void cso_trellis_inputs_free(cso_trellis_inputs_t *t) {
+    for (int c = 0; c < CSO_MAX_COMPS; c++) { free(t->samples[c]); free(t->raw[c]); free(t->coef[c]); t->samples[c] = NULL; t->raw[c] = NULL; t->coef[c] = NULL; }
 }

@@ -132,6 +132,21 @@ void cso_quality_tables(int quality, int profile, int force_baseline, uint16_t o
 void cso_fdct_islow(const uint8_t *samples8x8 /* row stride 8 */, int32_t out[64]);
 void cso_dering_block(int32_t level_shifted[64] /* natural order, in place */, int dc_quant);   /* mozjpeg preprocess_deringing [UPSTREAM-RECALL] */
 void cso_trellis_tables(const cso_image *im, int ci, uint8_t aclen[256], uint8_t dclen[17]);   /* rate tables of component ci's trellis pass */
+/* what the quantiser of cso_jpeg_compress (width = height = 0) / cso_jpeg_compress_resized sees, per component, captured on the same
+   decode -> (resize) -> forward path: the sample blocks in front of deringing, the DCT behind it, the rate tables of the trellis pass (those
+   of the scalar levels when p->trellis is 0) and the levels that come out.  Arrays [bh][bw][64], natural order; blocks outside
+   real_bw x real_bh hold zero samples and zero DCT.  For the tests that check the trellis quantiser against its stated cost model. */
+typedef struct {
+    int ncomp;
+    int h[CSO_MAX_COMPS], v[CSO_MAX_COMPS], bw[CSO_MAX_COMPS], bh[CSO_MAX_COMPS], real_bw[CSO_MAX_COMPS], real_bh[CSO_MAX_COMPS];
+    uint16_t qt[CSO_MAX_COMPS][64];
+    uint8_t aclen[CSO_MAX_COMPS][256], dclen[CSO_MAX_COMPS][17];
+    uint8_t *samples[CSO_MAX_COMPS];
+    int16_t *raw[CSO_MAX_COMPS];
+    int16_t *coef[CSO_MAX_COMPS];
+} cso_trellis_inputs_t;
+int  cso_trellis_inputs(const uint8_t *in, size_t n, const cso_enc_params *p, int width, int height, cso_trellis_inputs_t *out);
+void cso_trellis_inputs_free(cso_trellis_inputs_t *t);
 void cso_idct_islow(const int16_t coef[64], const uint16_t qt[64], uint8_t out[64]);
 int  cso_stock_script(int ncomp, int which, cso_scan *out); /* returns nscans */
 /* optimal Huffman table: freq[257] -> bits[17], huffval[256]; returns #symbols */

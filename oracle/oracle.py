@@ -45,6 +45,13 @@ class EncParams(C.Structure):
                 ("trellis", C.c_int), ("deringing", C.c_int)]
 
 
+class TrellisInputs(C.Structure):
+    _fields_ = [("ncomp", C.c_int), ("h", C.c_int * 4), ("v", C.c_int * 4), ("bw", C.c_int * 4), ("bh", C.c_int * 4),
+                ("real_bw", C.c_int * 4), ("real_bh", C.c_int * 4), ("qt", (C.c_uint16 * 64) * 4),
+                ("aclen", (C.c_uint8 * 256) * 4), ("dclen", (C.c_uint8 * 17) * 4),
+                ("samples", C.POINTER(C.c_uint8) * 4), ("raw", C.POINTER(C.c_int16) * 4), ("coef", C.POINTER(C.c_int16) * 4)]
+
+
 class Vp8Mb(C.Structure):
     _fields_ = [("segment", C.c_uint8), ("is_i4", C.c_uint8), ("ymode", C.c_uint8), ("uvmode", C.c_uint8), ("bmodes", C.c_uint8 * 16),
                 ("skip", C.c_uint8), ("alpha", C.c_uint8), ("pad", C.c_uint8 * 2), ("levels", (C.c_int16 * 16) * 25)]
@@ -108,6 +115,8 @@ def lib():
         L.cso_pixels_to_jpeg.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(EncParams), C.c_int, C.c_int, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
         L.cso_jpeg_compress_resized.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(EncParams), C.c_int, C.c_int,
                                                 C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
+        L.cso_trellis_inputs.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(EncParams), C.c_int, C.c_int, C.POINTER(TrellisInputs)]
+        L.cso_trellis_inputs_free.argtypes = [C.POINTER(TrellisInputs)]
         L.cso_last_error.restype = C.c_char_p
         L.cso_crc32.restype = C.c_uint32
         L.cso_crc32.argtypes = [C.c_uint32, C.c_char_p, C.c_size_t]
@@ -304,6 +313,29 @@ def jpeg_compress_resized(data, p, width, height):
     res = C.string_at(out, n.value)
     lib().cso_free(out)
     return res
+
+
+def trellis_inputs(src, p, width=0, height=0):
+    """what the quantiser of jpeg_compress (width = height = 0) / jpeg_compress_resized sees on the same decode -> (resize) -> forward path:
+    one dict per component with bw, bh, real_bw, real_bh, h, v, qt (natural order), aclen (256), dclen (17) -- the trellis pass's rate
+    tables, or those of the scalar levels when p.trellis is 0 -- and (bh, bw, 64) natural-order arrays: samples (uint8, in front of
+    deringing), raw (int16 DCT behind it, scaled by 8) and coef (the levels the oracle writes)"""
+    t = TrellisInputs()
+    _check(lib().cso_trellis_inputs(src, len(src), C.byref(p), width, height, C.byref(t)))
+    try:
+        comps = []
+        for c in range(t.ncomp):
+            bw, bh = t.bw[c], t.bh[c]
+            n = bw * bh * 64
+            comps.append(dict(bw=bw, bh=bh, real_bw=t.real_bw[c], real_bh=t.real_bh[c], h=t.h[c], v=t.v[c],
+                              qt=np.array(t.qt[c], dtype=np.int64), aclen=np.array(t.aclen[c], dtype=np.int64),
+                              dclen=np.array(t.dclen[c], dtype=np.int64),
+                              samples=np.ctypeslib.as_array(t.samples[c], shape=(n,)).reshape(bh, bw, 64).copy(),
+                              raw=np.ctypeslib.as_array(t.raw[c], shape=(n,)).reshape(bh, bw, 64).copy(),
+                              coef=np.ctypeslib.as_array(t.coef[c], shape=(n,)).reshape(bh, bw, 64).copy()))
+    finally:
+        lib().cso_trellis_inputs_free(C.byref(t))
+    return comps
 
 
 def pixels_to_jpeg(pix, p, width=0, height=0):
