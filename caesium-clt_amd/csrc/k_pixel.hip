@@ -645,7 +645,7 @@ __device__ __forceinline__ static uint32_t resample_quad_420(const PlaneView &v,
 
 __global__ void __launch_bounds__(256) k_resample_plane(const ImgDesc *imgs, const PlaneWork *work, const uint8_t *planes, uint8_t *oplanes) {
     const PlaneWork w = work[blockIdx.y];
-    if (w.mode == 0 || w.mode == 10) return;
+    if (w.mode == 0 || w.mode >= 10) return;
     const ImgDesc &im = imgs[w.image];
     const CompGeom gi = im.src[w.comp], go = im.out[w.comp];
     const int pitch_o = go.real_bw * 8, rows_o = go.real_bh * 8;
@@ -671,6 +671,100 @@ __global__ void __launch_bounds__(256) k_resample_plane(const ImgDesc *imgs, con
         case 7: out = resample_quad<2, 0>(v, W, H, och, y, x0); break;
         case 8: out = resample_quad<2, 1>(v, W, H, och, y, x0); break;
         default: out = resample_quad<2, 2>(v, W, H, och, y, x0); break;
+        }
+    }
+    *reinterpret_cast<uint32_t *>(oplanes + im.oplane_off[w.comp] + size_t(y) * pitch_o + x0) = out;
+}
+
+// ------------------------------------------------------------------------------------------------
+// every other layout (PlaneWork.mode CSH_MODE_ANY): 4:4:0, 4:1:1, 4:1:0, luma 3x1 / 1x4, Cb and Cr sampled differently on the decoder
+// side; h4v1 (4:1:1) on the encoder side.  One sample of the encoder-side plane: the DN box over full-resolution samples (csh_upsample_at),
+// with libjpeg's edge rules as in resample_one (oracle/jpeg_oracle.c forward_component: columns beyond W-1 replicate it, rows are clamped to
+// H-1, rows below the last downsampled one replicate it).
+template <int DN>
+__device__ __forceinline__ static int resample_any_one(const PlaneView &v, UpDesc u, int W, int H, int out_ch, int y, int xo) {
+    const int HX = DN == CSH_DN_FULL ? 1 : (DN == CSH_DN_H4V1 ? 4 : 2), VX = DN == CSH_DN_H2V2 ? 2 : 1;
+    const int ye = y < out_ch - 1 ? y : out_ch - 1;
+    int sum = 0;
+    CSH_UNROLL
+    for (int dy = 0; dy < VX; dy++) {
+        CSH_UNROLL
+        for (int dx = 0; dx < HX; dx++) {
+            int r = VX * ye + dy, xx = HX * xo + dx;
+            r = r > H - 1 ? H - 1 : r;
+            xx = xx > W - 1 ? W - 1 : xx;
+            sum += csh_upsample_at(v.p, v.pitch, v.cw, v.ch, u, r, xx);
+        }
+    }
+    if (DN == CSH_DN_H2V2) return (sum + ((xo & 1) ? 2 : 1)) >> 2;
+    if (DN == CSH_DN_H2V1) return (sum + (xo & 1)) >> 1;
+    if (DN == CSH_DN_H4V1) return (sum + 2) >> 2;
+    return sum;
+}
+template <int DN>
+__device__ __forceinline__ static uint32_t resample_any_quad(const PlaneView &v, UpDesc u, int W, int H, int out_ch, int y, int x0) {
+    uint32_t out = 0;
+    CSH_UNROLL
+    for (int i = 0; i < 4; i++) out |= uint32_t(resample_any_one<DN>(v, u, W, H, out_ch, y, x0 + i)) << (8 * i);
+    return out;
+}
+// The camera file recompressed at 4:1:1 (h2v2 fancy up, h4v1 box down), a quad of outputs from one full-resolution row r: 16 full-resolution
+// columns 4 x0 .. 4 x0 + 15 = plane columns 2 x0 .. 2 x0 + 7 and one neighbour either side, over plane rows r / 2 (nearer) and r / 2 -+ 1 (further).
+// Outputs (0, 1) and (2, 3) go in the 16-bit fields of one register each: quad420_fields gives E = centre of the output's even column, O = of
+// its odd one, L / R their outer neighbours, so each output is the four upsampled samples (E with L, E with O, O with E, O with R) summed.
+// last: plane column 2 x0 + 8 lies beyond the plane (pitch); libjpeg's neighbour there is the edge column 2 x0 + 7.
+__device__ __forceinline__ static uint32_t resample_quad_420_411(const PlaneView &v, int r, int x0) {
+    const int cy = r >> 1;
+    int fy = (r & 1) ? cy + 1 : cy - 1;
+    fy = fy < 0 ? 0 : (fy > v.ch - 1 ? v.ch - 1 : fy);
+    const bool last = 2 * x0 + 8 >= v.pitch;
+    Quad420 n[2], f[2];
+    {
+        const uint32_t *rp = reinterpret_cast<const uint32_t *>(v.p + size_t(cy) * v.pitch + 2 * x0);
+        const uint32_t a = rp[-1], b = rp[0], c = rp[1], d = last ? c >> 24 : rp[2];
+        n[0] = quad420_fields(a, b, c); n[1] = quad420_fields(b, c, d);
+    }
+    {
+        const uint32_t *rp = reinterpret_cast<const uint32_t *>(v.p + size_t(fy) * v.pitch + 2 * x0);
+        const uint32_t a = rp[-1], b = rp[0], c = rp[1], d = last ? c >> 24 : rp[2];
+        f[0] = quad420_fields(a, b, c); f[1] = quad420_fields(b, c, d);
+    }
+    const uint32_t M = 0x00FF00FFu;
+    uint32_t res[2];
+    CSH_UNROLL
+    for (int k = 0; k < 2; k++) {
+        // vertical step (3 * nearer row + further row, every field < 1024), then the horizontal one and jcsample's int_downsample
+        const uint32_t E = 3u * n[k].E + f[k].E, O = 3u * n[k].O + f[k].O, L = 3u * n[k].L + f[k].L, R = 3u * n[k].R + f[k].R;
+        const uint32_t s = ((3u * E + L + 0x00080008u) >> 4 & M) + ((3u * E + O + 0x00070007u) >> 4 & M) +
+                           ((3u * O + E + 0x00080008u) >> 4 & M) + ((3u * O + R + 0x00070007u) >> 4 & M);
+        res[k] = ((s + 0x00020002u) >> 2) & M;   // lo field: output 2k, hi field: output 2k + 1
+    }
+    return (res[0] & 0xFFu) | ((res[0] >> 8) & 0xFF00u) | ((res[1] & 0xFFu) << 16) | ((res[1] << 8) & 0xFF000000u);
+}
+__global__ void __launch_bounds__(256) k_resample_any(const ImgDesc *imgs, const PlaneWork *work, const uint8_t *planes, uint8_t *oplanes) {
+    const PlaneWork w = work[blockIdx.y];
+    if (w.mode != CSH_MODE_ANY) return;
+    const ImgDesc &im = imgs[w.image];
+    const CompGeom gi = im.src[w.comp], go = im.out[w.comp];
+    const int pitch_o = go.real_bw * 8, rows_o = go.real_bh * 8;
+    int q = blockIdx.x * blockDim.x + threadIdx.x;  // quad index
+    if (q >= (pitch_o >> 2) * rows_o) return;
+    int y = q / (pitch_o >> 2), x0 = (q - y * (pitch_o >> 2)) * 4;
+    PlaneView v;
+    v.p = planes + im.splane_off[w.comp]; v.pitch = gi.real_bw * 8; v.cw = gi.comp_w; v.ch = gi.comp_h;
+    const int W = im.enc_w, H = im.enc_h, och = go.comp_h;
+    const UpDesc u = w.up;
+    uint32_t out;
+    // vector path <=> the 16 full-resolution columns need no clamp, the left neighbour is inside the plane and the row's three dwords are too
+    if (u.cls == CSH_UP_H2V2 && w.dn == CSH_DN_H4V1 && x0 >= 4 && 2 * x0 + 8 <= v.pitch && 4 * x0 + 15 <= W - 1) {
+        const int ye = y < och - 1 ? y : och - 1;
+        out = resample_quad_420_411(v, ye > H - 1 ? H - 1 : ye, x0);
+    } else {
+        switch (w.dn) {
+        case CSH_DN_FULL: out = resample_any_quad<CSH_DN_FULL>(v, u, W, H, och, y, x0); break;
+        case CSH_DN_H2V2: out = resample_any_quad<CSH_DN_H2V2>(v, u, W, H, och, y, x0); break;
+        case CSH_DN_H2V1: out = resample_any_quad<CSH_DN_H2V1>(v, u, W, H, och, y, x0); break;
+        default: out = resample_any_quad<CSH_DN_H4V1>(v, u, W, H, och, y, x0); break;
         }
     }
     *reinterpret_cast<uint32_t *>(oplanes + im.oplane_off[w.comp] + size_t(y) * pitch_o + x0) = out;
@@ -886,6 +980,9 @@ void launch_idct_plane(hipStream_t st, const ImgDesc *imgs, const PlaneWork *wor
 }
 void launch_resample_plane(hipStream_t st, const ImgDesc *imgs, const PlaneWork *work, int nwork, uint32_t max_quads, const uint8_t *planes, uint8_t *oplanes) {
     if (nwork && max_quads) CSH_LAUNCH(k_resample_plane, dim3((max_quads + 255) / 256, nwork), dim3(256), st, imgs, work, planes, oplanes);
+}
+void launch_resample_any(hipStream_t st, const ImgDesc *imgs, const PlaneWork *work, int nwork, uint32_t max_quads, const uint8_t *planes, uint8_t *oplanes) {
+    if (nwork && max_quads) CSH_LAUNCH(k_resample_any, dim3((max_quads + 255) / 256, nwork), dim3(256), st, imgs, work, planes, oplanes);
 }
 void launch_plane_fdct(hipStream_t st, const ImgDesc *imgs, const PlaneWork *work, int nwork, int max_tiles, const DevQuant *quant,
                        const uint8_t *oplanes, int16_t *coef_out, int16_t *dct_raw, uint32_t raw_tile0, bool dering) {

@@ -59,6 +59,32 @@ __global__ void __launch_bounds__(256) k_planes_to_rgb(const ImgDesc *imgs, cons
     o[2] = uint8_t(b < 0 ? 0 : b > 255 ? 255 : b);
 }
 
+// any other layout (ResizeWork.in_kind CSH_RZ_ANY): every component, luma included, upsampled by its own method (types.h UpDesc) -- 4:4:0, 4:1:1,
+// 4:1:0, Cb and Cr sampled differently, luma not at the maximum factors.  Launched only for batches that hold such an image.
+__global__ void __launch_bounds__(256) k_planes_to_rgb_any(const ImgDesc *imgs, const ResizeWork *work, const uint8_t *planes, uint8_t *rgb) {
+    const ResizeWork w = work[blockIdx.y];
+    if (w.in_kind != CSH_RZ_ANY) return;
+    const ImgDesc &im = imgs[w.image];
+    const int W = im.width, H = im.height;
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= W * H) return;
+    int y = i / W, x = i - y * W;
+    int v[3];
+    for (int c = 0; c < 3; c++) {
+        const CompGeom &g = im.in[c];
+        v[c] = csh_upsample_at(planes + im.plane_off[c], g.real_bw * 8, g.comp_w, g.comp_h, w.up[c], y, x);
+    }
+    const int Y = v[0], cb = v[1] - 128, cr = v[2] - 128;
+    // jdcolor.c ycc_rgb_convert, SCALEBITS 16 (as k_planes_to_rgb)
+    int r = Y + ((91881 * cr + 32768) >> 16);
+    int b = Y + ((116130 * cb + 32768) >> 16);
+    int g = Y + ((-22554 * cb + (-46802 * cr + 32768)) >> 16);
+    uint8_t *o = rgb + w.rgb_src_off + size_t(i) * 3;
+    o[0] = uint8_t(r < 0 ? 0 : r > 255 ? 255 : r);
+    o[1] = uint8_t(g < 0 ? 0 : g > 255 ? 255 : g);
+    o[2] = uint8_t(b < 0 ? 0 : b > 255 ? 255 : b);
+}
+
 // vertical pass: tmp[oy][x][c] = sum_i src[left+i][x][c] * w[i]      (f32, no clamp).  A workgroup is a piece of ONE output row, so the
 // row's taps and weights are scalar loads; a lane takes four consecutive samples (one dword load per tap, four accumulators in the
 // order image-rs adds them)
@@ -212,10 +238,12 @@ __global__ void __launch_bounds__(256) k_rgb_to_planes(const ImgDesc *imgs, cons
 }
 
 void launch_resize(hipStream_t st, const ImgDesc *imgs, const ResizeWork *work, int nwork, const ResizeTap *taps, const float *weights,
-                   uint8_t *planes, uint8_t *rgb, float *tmp, uint32_t max_src_px, uint64_t max_tmp, uint64_t max_dst, uint32_t max_row_in, uint32_t max_out_w, uint32_t max_nh, bool to_planes) {
+                   uint8_t *planes, uint8_t *rgb, float *tmp, uint32_t max_src_px, uint64_t max_tmp, uint64_t max_dst, uint32_t max_row_in, uint32_t max_out_w, uint32_t max_nh, bool to_planes,
+                   bool any_layout) {
     (void)max_tmp;
     if (!nwork) return;
     CSH_LAUNCH(k_planes_to_rgb, dim3((max_src_px + 255) / 256, nwork), dim3(256), st, imgs, work, planes, rgb);
+    if (any_layout) CSH_LAUNCH(k_planes_to_rgb_any, dim3((max_src_px + 255) / 256, nwork), dim3(256), st, imgs, work, planes, rgb);
     if (resize_is_fused(max_row_in)) {   // (source and result lie in different stretches of the RGB pool: rgb_src_off / rgb_dst_off)
         if (max_row_in <= uint32_t(CSH_RZ_CAP_S)) CSH_LAUNCH_PHASED(k_lanczos_fused<CSH_RZ_CAP_S>, 2, dim3(max_nh, nwork), dim3(256), st, imgs, work, taps, weights, rgb, rgb);
         else CSH_LAUNCH_PHASED(k_lanczos_fused<CSH_RZ_CAP_L>, 2, dim3(max_nh, nwork), dim3(256), st, imgs, work, taps, weights, rgb, rgb);

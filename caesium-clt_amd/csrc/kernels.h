@@ -17,6 +17,35 @@ __host__ __device__ static inline size_t coef_index(uint32_t tile_base, int b, i
 #define CSH_RAW_OCT 8   // int16 elements between a block's octets
 __host__ __device__ static inline size_t raw_index(uint32_t tile_base, int b) { return size_t(tile_base) * CSH_TILE_I16 + size_t(b) * 64; }
 
+// one full-resolution sample (row r, column xx) of a decoded plane, any integral layout (types.h UpDesc; oracle/jpeg_oracle.c upsample_plane).
+// p: the plane, pitch bytes a row; cw / ch: the component's real size -- reads are clamped to it, which is libjpeg's edge rule for every method
+// (the first / last column and row of fancy upsampling weigh the edge sample itself).  The per-sample form of k_resample_any and k_planes_to_rgb_any.
+__device__ __forceinline__ static int csh_plane_at(const uint8_t *p, int pitch, int cw, int ch, int y, int x) {
+    y = y < 0 ? 0 : (y > ch - 1 ? ch - 1 : y);
+    x = x < 0 ? 0 : (x > cw - 1 ? cw - 1 : x);
+    return p[size_t(y) * pitch + x];
+}
+__device__ __forceinline__ static int csh_upsample_at(const uint8_t *p, int pitch, int cw, int ch, UpDesc u, int r, int xx) {
+    switch (u.cls) {
+    case CSH_UP_COPY: return csh_plane_at(p, pitch, cw, ch, r, xx);
+    case CSH_UP_H2V1: {   // jdsample h2v1_fancy_upsample: (3 nearer + further + 1 / 2) >> 2
+        const int cx = xx >> 1, nb = (xx & 1) ? cx + 1 : cx - 1;
+        return (3 * csh_plane_at(p, pitch, cw, ch, r, cx) + csh_plane_at(p, pitch, cw, ch, r, nb) + ((xx & 1) ? 2 : 1)) >> 2;
+    }
+    case CSH_UP_H1V2: {   // h1v2_fancy_upsample: the same triangle filter down the column
+        const int cy = r >> 1, fy = (r & 1) ? cy + 1 : cy - 1;
+        return (3 * csh_plane_at(p, pitch, cw, ch, cy, xx) + csh_plane_at(p, pitch, cw, ch, fy, xx) + ((r & 1) ? 2 : 1)) >> 2;
+    }
+    case CSH_UP_H2V2: {   // h2v2_fancy_upsample: vertical 3:1 column sums, then (3 nearer + further + 8 / 7) >> 4
+        const int cy = r >> 1, cx = xx >> 1, fy = (r & 1) ? cy + 1 : cy - 1, nb = (xx & 1) ? cx + 1 : cx - 1;
+        const int cs = 3 * csh_plane_at(p, pitch, cw, ch, cy, cx) + csh_plane_at(p, pitch, cw, ch, fy, cx);
+        const int cn = 3 * csh_plane_at(p, pitch, cw, ch, cy, nb) + csh_plane_at(p, pitch, cw, ch, fy, nb);
+        return (3 * cs + cn + ((xx & 1) ? 7 : 8)) >> 4;
+    }
+    default: return csh_plane_at(p, pitch, cw, ch, r / int(u.vx), xx / int(u.hx));   // int_upsample: replication
+    }
+}
+
 // ---- phase 0: entropy decode (k_decode.hip)
 void launch_decode_seq(hipStream_t st, const uint8_t *bits, ImgDesc *imgs, const DecScan *scans, const DevHuffSet *huffs,
                        int16_t *coef, int nimg, const uint32_t *need_seq);
@@ -69,12 +98,15 @@ void launch_plane_fdct(hipStream_t st, const ImgDesc *imgs, const PlaneWork *wor
                        const uint8_t *oplanes, int16_t *coef_out, int16_t *dct_raw, uint32_t raw_tile0, bool dering);
 void launch_resample_fdct_420(hipStream_t st, const ImgDesc *imgs, const PlaneWork *work, int nwork, int max_tiles, const DevQuant *quant,
                               const uint8_t *planes, int16_t *coef_out, int16_t *dct_raw, uint32_t raw_tile0, bool dering);
+// every layout k_resample_plane does not take (PlaneWork.mode CSH_MODE_ANY): launched only when a batch has such items
+void launch_resample_any(hipStream_t st, const ImgDesc *imgs, const PlaneWork *work, int nwork, uint32_t max_quads, const uint8_t *planes, uint8_t *oplanes);
 void launch_fix_dummy(hipStream_t st, const ImgDesc *imgs, int nimg, int max_blocks, int16_t *coef_out);
 
 // resize branch (k_resize.hip): decoded planes -> RGB -> Lanczos3 (f32, image-rs order) -> full-resolution YCbCr planes
 bool resize_is_fused(uint32_t max_row_in);   // both Lanczos passes in one kernel, no f32 intermediate image (the batch's widest source row fits LDS)
 void launch_resize(hipStream_t st, const ImgDesc *imgs, const ResizeWork *work, int nwork, const ResizeTap *taps, const float *weights,
-                   uint8_t *planes, uint8_t *rgb, float *tmp, uint32_t max_src_px, uint64_t max_tmp, uint64_t max_dst, uint32_t max_row_in, uint32_t max_out_w, uint32_t max_nh, bool to_planes);
+                   uint8_t *planes, uint8_t *rgb, float *tmp, uint32_t max_src_px, uint64_t max_tmp, uint64_t max_dst, uint32_t max_row_in, uint32_t max_out_w, uint32_t max_nh, bool to_planes,
+                   bool any_layout = false);   // any_layout: the batch has ResizeWork items of CSH_RZ_ANY (k_planes_to_rgb_any)
 
 // ---- phases 2-5: entropy encode (k_entropy.hip)
 // tokens -> runs -> tables -> chunk sizes -> (scan) -> pack.  A token is one u32 (k_entropy.hip); the tokens of one (scan, 256-unit

@@ -173,6 +173,7 @@ struct csh_batch {
     uint32_t ntiles = 0, ntiles_in = 0, ntiles_out = 0, max_tiles = 0, max_units = 0, max_dummy = 0;
     uint64_t total_units = 0, total_words = 0, plane_bytes = 0, oplane_bytes = 0;
     uint32_t max_quads = 0;
+    bool any_layout = false, any_layout_rgb = false;   // some work item is CSH_MODE_ANY / some resize item CSH_RZ_ANY: the batch launches k_resample_any / k_planes_to_rgb_any
     int ntables = 0;
     uint64_t raw_bytes_cap = 0, out_cap = 0;
 
@@ -411,6 +412,19 @@ void csh_compute_dimensions(int ow, int oh, int dw, int dh, int &nw, int &nh) {
     if (nh < 1) nh = 1;
 }
 
+// decoded plane -> full resolution: libjpeg-turbo's choice of upsampling method (jdsample.c jinit_upsampler), cw the downsampled width
+static UpDesc up_desc(int hx, int vx, int cw) {
+    UpDesc u; u.hx = uint8_t(hx); u.vx = uint8_t(vx); u.pad = 0;
+    if (hx == 1 && vx == 1) u.cls = CSH_UP_COPY;
+    else if (hx == 2 && vx == 1 && cw > 2) u.cls = CSH_UP_H2V1;
+    else if (hx == 1 && vx == 2) u.cls = CSH_UP_H1V2;
+    else if (hx == 2 && vx == 2 && cw > 2) u.cls = CSH_UP_H2V2;
+    else u.cls = CSH_UP_REP;
+    return u;
+}
+// full resolution -> encoder plane (jcsample.c): the output layouts are 4:4:4, 4:2:2, 4:2:0 and 4:1:1 (plan_item)
+static int dn_kind(int hx, int vx) { return hx == 1 ? CSH_DN_FULL : (hx == 4 ? CSH_DN_H4V1 : (vx == 2 ? CSH_DN_H2V2 : CSH_DN_H2V1)); }
+
 static int plan_item(Item &it, const CCSParameters &p, bool lossless) {
     const JpegInfo &in = it.in;
     if (in.ncomp != 1 && in.ncomp != 3) { it.msg = "unsupported component count (CMYK/YCCK not on the device path yet)"; return CS_ERR_JPEG_FEATURE; }
@@ -438,13 +452,20 @@ static int plan_item(Item &it, const CCSParameters &p, bool lossless) {
     if (ss == 0) ss = 420;
     for (int c = 0; c < in.ncomp; c++) { o.comp[c].id = c + 1; o.comp[c].h = o.comp[c].v = 1; o.comp[c].tq = c ? 1 : 0; }
     if (in.ncomp == 3) {
-        bool in444 = in.comp[0].h == 1 && in.comp[0].v == 1, in420 = in.comp[0].h == 2 && in.comp[0].v == 2;
-        bool in422 = in.comp[0].h == 2 && in.comp[0].v == 1;
-        bool chroma11 = in.comp[1].h == 1 && in.comp[1].v == 1 && in.comp[2].h == 1 && in.comp[2].v == 1;
-        if (!chroma11 || !(in444 || in420 || in422)) { it.msg = "input chroma sampling other than 4:4:4 / 4:2:2 / 4:2:0 not on the device path yet"; return CS_ERR_JPEG_FEATURE; }
+        // any layout libjpeg decodes: every component's up factors hmax / h and vmax / v integers in 1..4 (jdsample.c int_upsample), at most
+        // 10 blocks per MCU (D_MAX_BLOCKS_IN_MCU)
+        int blocks = 0;
+        for (int c = 0; c < 3; c++) {
+            const JComp &k = in.comp[c];
+            blocks += k.h * k.v;
+            if (in.hmax % k.h || in.vmax % k.v) { it.msg = "fractional chroma sampling ratio (component factors do not divide the largest ones)"; return CS_ERR_JPEG_FEATURE; }
+            if (in.hmax / k.h > 4 || in.vmax / k.v > 4) { it.msg = "chroma sampling ratio above 4"; return CS_ERR_JPEG_FEATURE; }
+        }
+        if (blocks > 10) { it.msg = "more than 10 blocks per MCU"; return CS_ERR_JPEG_FEATURE; }
         if (ss == 420) { o.comp[0].h = 2; o.comp[0].v = 2; }
         else if (ss == 422) { o.comp[0].h = 2; o.comp[0].v = 1; }
-        else if (ss != 444) { it.msg = "output chroma subsampling 4:1:1 not on the device path yet"; return CS_ERR_JPEG_FEATURE; }
+        else if (ss == 411) { o.comp[0].h = 4; o.comp[0].v = 1; }
+        else if (ss != 444) { it.msg = "unknown output chroma subsampling"; return CS_ERR_JPEG_FEATURE; }
     }
     jpeg_geometry(o);
     return 0;
@@ -1041,12 +1062,14 @@ static int batch_create(const CByteArray *inputs, size_t count, const CCSParamet
         if (!b->lossless)
             for (int c = 0; c < in.ncomp; c++) {
                 PlaneWork w; w.image = img_index; w.comp = c;
-                bool in_full = in.comp[c].h == in.hmax && in.comp[c].v == in.vmax;
-                bool out_full = o.comp[c].h == o.hmax && o.comp[c].v == o.vmax;
-                int in_kind = in_full ? 0 : (in.comp[c].v == in.vmax ? 2 : 1);    // 0 full, 1 h2v2, 2 h2v1
-                int out_kind = out_full ? 0 : (o.comp[c].v == o.vmax ? 2 : 1);
-                w.mode = (in_kind == 0 && out_kind == 0) ? 0 : 1 + 3 * in_kind + out_kind;
-                if (resized) w.mode = 1 + out_kind;   // encoder side is fed full-resolution planes of the resized image (k_resize.hip)
+                w.up = resized ? up_desc(1, 1, 0) : up_desc(in.hmax / in.comp[c].h, in.vmax / in.comp[c].v, in.comp[c].comp_w);
+                w.dn = dn_kind(o.hmax / o.comp[c].h, o.vmax / o.comp[c].v);
+                // the layouts k_resample_plane takes keep its mode numbers (in: 0 full, 1 h2v2, 2 h2v1 by the up factors); every other one is CSH_MODE_ANY
+                const int in_kind = (w.up.hx == 1 && w.up.vx == 1) ? 0 : (w.up.hx == 2 && w.up.vx == 2) ? 1 : (w.up.hx == 2 && w.up.vx == 1) ? 2 : -1;
+                if (in_kind < 0 || w.dn == CSH_DN_H4V1) w.mode = CSH_MODE_ANY;
+                else if (resized) w.mode = 1 + w.dn;   // encoder side is fed full-resolution planes of the resized image (k_resize.hip)
+                else w.mode = (in_kind == 0 && w.dn == CSH_DN_FULL) ? 0 : 1 + 3 * in_kind + w.dn;
+                if (w.mode == CSH_MODE_ANY) b->any_layout = true;
                 // the camera case (4:2:0 kept, no resize) goes through k_resample_fdct_420 and has no encoder-side plane
                 const bool fused = w.mode == 5 && !resized && im.in[c].comp_w > 2 && im.in[c].real_bw == im.out[c].real_bw && im.in[c].real_bh == im.out[c].real_bh &&
                                    im.in[c].comp_w == im.out[c].comp_w && im.in[c].comp_h == im.out[c].comp_h && !getenv("CSH_NO_FUSED_420");
@@ -1077,6 +1100,13 @@ static int batch_create(const CByteArray *inputs, size_t count, const CCSParamet
             memset(&rw, 0, sizeof rw);
             rw.image = img_index; rw.nw = o.width; rw.nh = o.height;
             rw.in_kind = in.ncomp == 1 ? 0 : ((in.comp[1].h == in.hmax && in.comp[1].v == in.vmax) ? 0 : (in.comp[1].v == in.vmax ? 2 : 1));
+            for (int c = 0; c < in.ncomp; c++) rw.up[c] = up_desc(in.hmax / in.comp[c].h, in.vmax / in.comp[c].v, in.comp[c].comp_w);
+            if (in.ncomp == 3) {   // k_planes_to_rgb takes full luma and Cb, Cr both 1x1 (full), 2x2 or 2x1 below it
+                auto same = [&](int c, int hx, int vx) { return rw.up[c].hx == hx && rw.up[c].vx == vx; };
+                const bool legacy = same(0, 1, 1) && rw.up[1].hx == rw.up[2].hx && rw.up[1].vx == rw.up[2].vx &&
+                                    (same(1, 1, 1) || same(1, 2, 2) || same(1, 2, 1));
+                if (!legacy) { rw.in_kind = CSH_RZ_ANY; b->any_layout_rgb = true; }
+            }
             if (px) rw.in_kind = -1;   // the RGB of this image is not made from decoded planes: it is copied in below (csh_batch_create_from_pixels)
             const uint64_t src_bytes = uint64_t(in.width) * in.height * in.ncomp, dst_bytes = uint64_t(o.width) * o.height * in.ncomp;
             rw.rgb_src_off = b->rgb_bytes; b->rgb_bytes += (src_bytes + 63) & ~uint64_t(63);
@@ -1785,7 +1815,7 @@ static int run_once(csh_batch *b, csh_timing *t, bool requant_only) {
     launch_idct_plane(st, b->d_imgs.p, b->d_pwork.p, nw, b->max_tiles, b->d_quants.p, b->d_coef.p, b->d_planes.p);
     MARK();
     launch_resize(st, b->d_imgs.p, b->d_rwork.p, int(b->rwork.size()), b->d_rtaps.p, b->d_rweights.p, b->d_planes.p, b->d_rgb.p, b->d_rtmp.p,
-                  b->max_src_px, b->max_tmp, b->max_dst, b->max_row_in, b->max_out_w, b->max_nh, !(b->webp || b->rgb_out));
+                  b->max_src_px, b->max_tmp, b->max_dst, b->max_row_in, b->max_out_w, b->max_nh, !(b->webp || b->rgb_out), b->any_layout_rgb);
     MARK();
     if (b->webp) return run_webp(b, t, ev, slot);
     if (b->rgb_out) return run_rgb_only(b, t, ev, slot);
@@ -1793,6 +1823,7 @@ static int run_once(csh_batch *b, csh_timing *t, bool requant_only) {
     launch_xform_direct(st, b->d_imgs.p, b->d_pwork.p, nw, b->max_tiles, b->d_quants.p, b->d_coef.p, b->d_coef.p, rawp, b->ntiles_in, b->dering);
     MARK();
     launch_resample_plane(st, b->d_imgs.p, b->d_pwork.p, nw, b->max_quads, b->d_planes.p, b->d_oplanes.p);
+    if (b->any_layout) launch_resample_any(st, b->d_imgs.p, b->d_pwork.p, nw, b->max_quads, b->d_planes.p, b->d_oplanes.p);
     launch_plane_fdct(st, b->d_imgs.p, b->d_pwork.p, nw, b->max_tiles, b->d_quants.p, b->d_oplanes.p, b->d_coef.p, rawp, b->ntiles_in, b->dering);
     launch_resample_fdct_420(st, b->d_imgs.p, b->d_pwork.p, nw, b->max_tiles, b->d_quants.p, b->d_planes.p, b->d_coef.p, rawp, b->ntiles_in, b->dering);
     MARK();

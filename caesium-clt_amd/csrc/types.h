@@ -151,15 +151,32 @@ struct DevQuant {
     uint32_t sh[64];
 };
 
+// How one component's plane relates to full resolution, per component.  Decoder side: libjpeg-turbo's upsampling method (jdsample.c
+// jinit_upsampler) for up factors hx = hmax / h, vx = vmax / v -- copy when both are 1; h2v1 and h2v2 fancy only when the downsampled width is
+// greater than 2; h1v2 fancy always; integral replication for every other ratio (and for h2v1 / h2v2 on planes of width <= 2).
+enum { CSH_UP_COPY = 0, CSH_UP_H2V2 = 1, CSH_UP_H2V1 = 2, CSH_UP_H1V2 = 3, CSH_UP_REP = 4 };
+// Encoder side: jcsample.c's downsampler -- none, h2v2 (bias 1,2,..), h2v1 (bias 0,1,..), h4v1 (int_downsample: (sum of 4 + 2) >> 2)
+enum { CSH_DN_FULL = 0, CSH_DN_H2V2 = 1, CSH_DN_H2V1 = 2, CSH_DN_H4V1 = 3 };
+struct UpDesc { uint8_t cls, hx, vx, pad; };   // decoded plane -> full resolution: CSH_UP_* and the up factors
+
 // work item of the pixel kernels: one component of one image
+#define CSH_MODE_ANY 11
 struct PlaneWork {
     int image, comp;
-    int mode;  // 0: full-res in and out (IDCT->FDCT in one lane); 10: h2v2 kept, no resize (k_resample_fdct_420); else 1 + 3*in_kind + out_kind with kinds 0 full, 1 h2v2, 2 h2v1
+    // 0: full-res in and out (IDCT->FDCT in one lane); 10: h2v2 kept, no resize (k_resample_fdct_420); 1 + 3*in_kind + out_kind with kinds 0 full,
+    // 1 h2v2, 2 h2v1 for the layouts k_resample_plane takes (in: up factors 1x1, 2x2, 2x1 -- full resolution on the resize path; out: none, h2v2,
+    // h2v1); CSH_MODE_ANY: every other layout, through k_resample_any from `up` and `dn`
+    int mode;
+    UpDesc up;     // the decoded plane (resize path: the full-resolution plane of the resized image, CSH_UP_COPY)
+    int dn;        // CSH_DN_*: the encoder's downsampling
 };
 
 // resize path work item (k_resize.hip): one image
+#define CSH_RZ_ANY (-2)
 struct ResizeWork {
-    int image, in_kind;            // in_kind: how the decoded chroma planes relate to full resolution (0 full, 1 h2v2, 2 h2v1)
+    int image, in_kind;            // in_kind: how the decoded chroma planes relate to full resolution (0 full, 1 h2v2, 2 h2v1); -1 a pixel source;
+                                   // CSH_RZ_ANY: any other layout, per component from `up` (k_planes_to_rgb_any)
+    UpDesc up[CSH_MAX_COMPS];
     int nw, nh;                    // new size
     uint64_t rgb_src_off, rgb_dst_off;  // byte offsets in the RGB pool (W*H*nc source, nw*nh*nc resized)
     uint64_t tmp_off;              // float offset in the f32 pool (nh*W*nc)
