@@ -426,10 +426,12 @@ __global__ void __launch_bounds__(CSP_WAVE_THREADS * HUFF_WAVES) k_png_huff(cons
             if (S.lens[256] == 0) { err = CSP_ERR_BAD_PNG; break; }
         }
         {
+            // an incomplete code only as a single codeword of length 1 (zlib inflate_table's "max != 1", libdeflate); the fixed distance
+            // code is incomplete by definition
             int r = build_code(S.lens, nlen, S.lcount, S.offs, S.lsorted, S.lroot, LROOT, S.lresume);
-            if (type == 2 && (r < 0 || (r > 0 && nlen - int(S.lcount[0]) != 1))) { err = CSP_ERR_BAD_PNG; break; }
+            if (type == 2 && (r < 0 || (r > 0 && (nlen - int(S.lcount[0]) != 1 || S.lcount[1] != 1u)))) { err = CSP_ERR_BAD_PNG; break; }
             r = build_code(S.lens + 288, ndist, S.dcount, S.offs, S.dsorted, S.droot, DROOT, S.dresume);
-            if (type == 2 && (r < 0 || (r > 0 && ndist - int(S.dcount[0]) != 1))) { err = CSP_ERR_BAD_PNG; break; }   // the fixed distance code is incomplete by definition
+            if (type == 2 && (r < 0 || (r > 0 && (ndist - int(S.dcount[0]) != 1 || S.dcount[1] != 1u)))) { err = CSP_ERR_BAD_PNG; break; }
         }
         // The symbols, HUFF_SUB bits per lane and round.  Where a prefix-coded stream is entered matters only for a few tokens: a walk that
         // starts at a wrong bit falls into step with the true one after a handful of codes.  So every lane of every wave walks its own

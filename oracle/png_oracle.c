@@ -155,10 +155,11 @@ static int inflate_raw(ibits *s, uint8_t *out, size_t cap, size_t *produced) {
                 }
             }
             if (lens[256] == 0) return -9;
+            /* an incomplete code only as a single codeword of length 1 (zlib inflate_table's "max != 1", libdeflate) */
             int r = hbuild(&lc, lens, nlen);
-            if (r < 0 || (r > 0 && nlen - lc.count[0] != 1)) return -10;
+            if (r < 0 || (r > 0 && (nlen - lc.count[0] != 1 || lc.count[1] != 1))) return -10;
             r = hbuild(&dc, lens + nlen, ndist);
-            if (r < 0 || (r > 0 && ndist - dc.count[0] != 1)) return -11;
+            if (r < 0 || (r > 0 && (ndist - dc.count[0] != 1 || dc.count[1] != 1))) return -11;
         }
         for (;;) {
             int sym = hdecode(s, &lc);
