@@ -474,7 +474,7 @@ void launch_list_stats(hipStream_t st, const EncCtx &c) { if (c.nlist_slots) CSH
 void launch_list_pack(hipStream_t st, const EncCtx &c) { if (c.nlist_slots) CSH_LAUNCH(k_list_pack, dim3((c.nlist_slots + 3) / 4), dim3(4 * CSP_WAVE_THREADS), st, c); }
 // ---- the slots of the work items: one workgroup per work item, one lane per 256-unit chunk.  Under the scan search a 1080p image has ~3.9 k slots in 58 work
 // items: built on the host they were 64 MB of records per 256 files to write and to upload in front of the first kernel (the boundary call paid ~15 ms of
-// every 50 for them); the host only counts them now (pipeline.cpp add_works).  Slots between the stages belong to no work item and stay zero.
+// every 50 for them); the host only counts them now (batch_plan.cpp add_works).  Slots between the stages belong to no work item and stay zero.
 __global__ void __launch_bounds__(64) k_make_slots(const ScanWork *works, uint32_t nworks, const EncScan *script, const NzList *nzlists, SlotRec *slots, uint32_t *slot_work, uint32_t *list_slots,
                                                    uint32_t *tok_slots) {
     const uint32_t wi = blockIdx.x;
@@ -497,7 +497,7 @@ __global__ void __launch_bounds__(64) k_make_slots(const ScanWork *works, uint32
         (listed ? list_slots : tok_slots)[w.ls_base + j] = w.first_chunk + j;
     }
 }
-// the scan search re-points work items to the lists of the point transform it chose (pipeline.cpp search_decide): their slots follow
+// the scan search re-points work items to the lists of the point transform it chose (scan_search.cpp search_decide): their slots follow
 __global__ void __launch_bounds__(64) k_rebind_slots(const ScanWork *works, uint32_t nworks, const NzList *nzlists, SlotRec *slots) {
     const uint32_t wi = blockIdx.x;
     if (wi >= nworks) return;

@@ -73,7 +73,7 @@ __global__ void __launch_bounds__(256) k_scan_down(const uint32_t *in, uint64_t 
 }
 size_t exclusive_scan_tmp_bytes(uint64_t n) { return size_t((n + CSH_SCAN_STRETCH - 1) / CSH_SCAN_STRETCH + 2) * sizeof(uint64_t); }
 // CONTRACT: out[i] is the true 64-bit prefix wherever every stretch of 64 consecutive inputs sums below 2^32 (sizes, counts: every caller but one).  The DC
-// differences (pipeline.cpp: dcdiff reinterpreted as uint32_t, negative values ~ 2^32) break that premise on purpose: their prefix is only right modulo
+// differences (batch_run.cpp: dcdiff reinterpreted as uint32_t, negative values ~ 2^32) break that premise on purpose: their prefix is only right modulo
 // 2^32, and k_dc_scatter uses the low 32 bits of the DIFFERENCE of two prefixes only.
 void launch_exclusive_scan(hipStream_t st, const uint32_t *in, uint64_t *out, uint64_t n, void *tmp, size_t tmp_bytes) {
     uint64_t *sums = static_cast<uint64_t *>(tmp);

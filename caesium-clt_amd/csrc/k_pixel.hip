@@ -858,7 +858,7 @@ __global__ void __launch_bounds__(256) k_resample_fdct_420(const ImgDesc *__rest
     }
     // the whole 10 x 16-byte window first (one wait for memory, not ten): row j = plane row y0 - 1 + j, bytes x0 - 4 .. x0 + 11.  The first
     // block of a row reads four bytes in front of its row and the last four bytes behind it (the neighbouring rows' ends; the plane pool has 64
-    // bytes of slack at either end, pipeline.cpp) and replaces them with its own edge sample.
+    // bytes of slack at either end, batch_plan.cpp) and replaces them with its own edge sample.
     Row16 rows[10];
     CSH_UNROLL
     for (int j = 0; j < 10; j++) {

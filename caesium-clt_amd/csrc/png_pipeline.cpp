@@ -702,7 +702,7 @@ static int reduce_step(csp_batch *b) {
 }
 
 // conversion to WebP: pixels -> 8-bit RGB -> the VP8 encoder of webp_kernels.h (statement: oracle/webp_oracle.c).  The output pool is
-// sized per macroblock and grows when a file overflows it, as in the JPEG -> WebP path (pipeline.cpp: run_webp)
+// sized per macroblock and grows when a file overflows it, as in the JPEG -> WebP path (batch_run.cpp: Run::webp)
 static int run_to_webp(csp_batch *b) {
     hipStream_t st = b->stream;
     const int nimg = int(b->wimgs.size());

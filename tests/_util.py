@@ -33,7 +33,7 @@ def emul_api():
 
 
 def device_profile():
-    """the JPEG profile the device library is in (pipeline.cpp batch_create): unset = "mozjpeg", what libcaesium's -q runs"""
+    """the JPEG profile the device library is in (batch_plan.cpp PlanSwitches): unset = "mozjpeg", what libcaesium's -q runs"""
     return os.environ.get("CSH_PROFILE") or "mozjpeg"
 
 

@@ -1,4 +1,4 @@
-/* The pixel kernels' scalar quantiser (caesium-clt_amd/csrc/k_pixel.hip quant_one; the reciprocal: pipeline.cpp make_quant) against the integer
+/* The pixel kernels' scalar quantiser (caesium-clt_amd/csrc/k_pixel.hip quant_one; the reciprocal: batch_plan.cpp make_quant) against the integer
    statement of libjpeg's rule, sign(t) * ((|t| + d / 2) / d) with d = 8 q: every 16-bit table value, every |t| <= 2^15.
    glibc's fmaf is the correctly rounded fused multiply-add v_fma_f32 computes.  Run by tests/test_quant_reciprocal.py. */
 #include <math.h>
