@@ -22,10 +22,18 @@ extern "C" int csl_encode_pixels(const csp_pixels *px, size_t count, int device,
         for (size_t i = 0; i < count; i++) results[i] = make_res(CS_ERR_NO_DEVICE, "no HIP device available (libcaesium_hip has no CPU path)");
         return int(count);
     }
+    // the coder, read on every call: unset / empty / "plain" = literals only (the bytes oracle/png_oracle.c cso_vp8l_encode states), "refs" = backward
+    // references and a colour cache (k_vp8l_refs.hip)
+    const char *mode = getenv("CSH_VP8L");
+    const bool refs = mode && !strcmp(mode, "refs");
+    if (mode && *mode && !refs && strcmp(mode, "plain")) {
+        for (size_t i = 0; i < count; i++) results[i] = make_res(CS_ERR_UNSUPPORTED, "CSH_VP8L names no lossless WebP coder (plain, refs)");
+        return int(count);
+    }
     int failed = 0;
     std::vector<csw::Vp8lImg> imgs;
     std::vector<size_t> at;
-    uint64_t work = 0, modes = 0, out = 0, max_px = 0;
+    uint64_t work = 0, modes = 0, out = 0, max_px = 0, cst = 0;
     uint32_t max_blocks = 0;
     for (size_t i = 0; i < count; i++) {
         const uint32_t ch = px[i].channels;
@@ -41,7 +49,12 @@ extern "C" int csl_encode_pixels(const csp_pixels *px, size_t count, int device,
         im.mode_off = modes; modes += (uint64_t(im.bw) * im.bh + 63) & ~uint64_t(63);
         const uint64_t cap = 8 * npx + 2 * uint64_t(im.bw) * im.bh + 8192;   // four codes of at most 15 bits per pixel, the mode image, the code descriptions
         if (cap > 0xFFFFFFF0ull) { results[i] = make_res(CS_ERR_UNSUPPORTED, "picture too large for one lossless WebP batch item"); failed++; continue; }
-        im.out_off = out; im.out_cap = uint32_t(cap); out += (cap + 255) & ~uint64_t(255);
+        im.out_off = out; im.out_cap = uint32_t(cap); out += (cap + 255) & ~uint64_t(255);   // (the refs stream is written only where it is the smaller one)
+        if (refs) {
+            im.nchunk = uint32_t((npx + csw::VP8L_CHUNK - 1) / csw::VP8L_CHUNK);
+            im.tok_off = im.res_off; im.hit_off = im.res_off;   // one entry per pixel, like the residuals
+            im.cst_off = cst; cst += uint64_t(im.nchunk) * csw::VP8L_CACHE_STATE;
+        }
         max_px = std::max(max_px, npx); max_blocks = std::max(max_blocks, im.bw * im.bh);
         imgs.push_back(im); at.push_back(i);
     }
@@ -50,14 +63,23 @@ extern "C" int csl_encode_pixels(const csp_pixels *px, size_t count, int device,
     bool have_st = false;
     DevBuf<csw::Vp8lImg> d_imgs;
     DevBuf<uint32_t> d_work, d_hist, d_len, d_status;
-    DevBuf<uint8_t> d_modes, d_out;
+    DevBuf<uint8_t> d_modes, d_out, d_hit, d_lens;
+    DevBuf<uint64_t> d_tok, d_cst;
+    DevBuf<uint32_t> d_rhist, d_pick;
     std::vector<uint32_t> len(imgs.size()), status(imgs.size());
     bool ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
     have_st = ok;
     ok = ok && !d_imgs.upload(imgs, st) && !d_work.alloc(work + 64) && !d_hist.alloc(imgs.size() * 1024 + 8) && !d_hist.zero(st) && !d_len.alloc(imgs.size() + 1) && !d_status.alloc(imgs.size() + 1) &&
          !d_modes.alloc(modes + 64) && !d_out.alloc(out + 256);
+    if (ok && refs)
+        ok = !d_tok.alloc(work + 64) && !d_hit.alloc(work + 64) && !d_cst.alloc(cst + 64) && !d_rhist.alloc(imgs.size() * csw::VP8L_NOPT * csw::VP8L_HIST + 8) && !d_rhist.zero(st) &&
+             !d_lens.alloc(imgs.size() * csw::VP8L_LENS + 8) && !d_pick.alloc(imgs.size() * 4 + 4);
     if (ok) {
-        csw::launch_vp8l_encode(st, d_imgs.p, int(imgs.size()), max_blocks, max_px, d_work.p, d_modes.p, d_hist.p, d_out.p, d_len.p, d_status.p);
+        if (refs) {
+            const csw::Vp8lRefs pools = {d_tok.p, d_hit.p, d_cst.p, d_rhist.p, d_lens.p, d_pick.p};
+            csw::launch_vp8l_encode_refs(st, d_imgs.p, int(imgs.size()), max_blocks, max_px, d_work.p, d_modes.p, d_hist.p, pools, d_out.p, d_len.p, d_status.p);
+        } else
+            csw::launch_vp8l_encode(st, d_imgs.p, int(imgs.size()), max_blocks, max_px, d_work.p, d_modes.p, d_hist.p, d_out.p, d_len.p, d_status.p);
         ok = hipMemcpyAsync(len.data(), d_len.p, len.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
              hipMemcpyAsync(status.data(), d_status.p, status.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess && hipGetLastError() == hipSuccess;
     }

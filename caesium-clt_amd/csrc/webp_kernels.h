@@ -44,9 +44,40 @@ struct Vp8lImg {
     uint64_t mode_off;     // predictor mode of every block (byte index)
     uint64_t out_off;      // output file region
     uint32_t out_cap;
+    // CSH_VP8L=refs only (k_vp8l_refs.hip); zero in plain mode
+    uint32_t nchunk;       // chunks of VP8L_CHUNK positions of the scan order
+    uint64_t tok_off;      // one u64 per pixel (u64 index into the token pool): the match candidate, then the parse's token
+    uint64_t hit_off;      // one byte per pixel: bit k = the pixel hits the colour cache of option k (vp8l_cache_bits)
+    uint64_t cst_off;      // colour-cache contents in front of every chunk, every option (u64 index): nchunk x VP8L_CACHE_STATE
 };
 void launch_vp8l_encode(hipStream_t st, const Vp8lImg *imgs, int nimg, uint32_t max_blocks, uint64_t max_pixels, uint32_t *work, uint8_t *modes, uint32_t *hist, uint8_t *out, uint32_t *file_len,
                         uint32_t *status);
+// the same with backward references and a colour cache (CSH_VP8L=refs, k_vp8l_refs.hip); a picture whose stream would not be smaller is written by the plain coder
+enum : uint32_t {
+    VP8L_CHUNK = 4096,                    // positions per wave in the match, parse and cache stages
+    VP8L_MAX_LEN = 4096,                  // the format's longest copy
+    VP8L_WINDOW = (1u << 20) - 120,       // the farthest distance (libwebp's)
+    VP8L_NOPT = 4,                        // colour-cache sizes tried per picture: vp8l_cache_bits(0 .. 3)
+    VP8L_CACHE_STATE = 16 + 128 + 1024,   // slots of all the options with a cache
+    VP8L_GREEN_MAX = 256 + 24 + 1024,     // the widest green alphabet
+    VP8L_HIST = VP8L_GREEN_MAX + 3 * 256 + 40,   // counts of one option: green, red, blue, alpha, distance
+    VP8L_LENS = 5 * VP8L_GREEN_MAX,       // code lengths of the chosen option, VP8L_GREEN_MAX bytes per code
+};
+__host__ __device__ static inline uint32_t vp8l_cache_bits(uint32_t opt) { return opt == 0 ? 0u : 1u + 3u * opt; }   // 0 (no cache), 4, 7, 10
+struct Vp8lRefs {
+    uint64_t *tok;         // tokens (Vp8lImg::tok_off)
+    uint8_t *hit;          // cache hits (hit_off)
+    uint64_t *cst;         // cache contents (cst_off)
+    uint32_t *hist;        // per picture VP8L_NOPT x VP8L_HIST counts, zeroed by the caller
+    uint8_t *lens;         // per picture VP8L_LENS
+    uint32_t *pick;        // per picture 4 words: 1 = the refs stream is smaller, the option, the two streams' bits behind the common header
+};
+void launch_vp8l_encode_refs(hipStream_t st, const Vp8lImg *imgs, int nimg, uint32_t max_blocks, uint64_t max_pixels, uint32_t *work, uint8_t *modes, uint32_t *hist, const Vp8lRefs &refs,
+                             uint8_t *out, uint32_t *file_len, uint32_t *status);
+// pieces of launch_vp8l_encode (k_vp8l_enc.hip) the refs coder runs as they are: the front end, and the plain pack for the pictures whose pick[4 i] is 0 (pick = nullptr: all)
+void launch_vp8l_front(hipStream_t st, const Vp8lImg *imgs, int nimg, uint32_t max_blocks, uint64_t max_pixels, uint32_t *work, uint8_t *modes, uint32_t *hist);
+void launch_vp8l_pack_plain(hipStream_t st, const Vp8lImg *imgs, int nimg, const uint32_t *work, const uint8_t *modes, const uint32_t *hist, const uint32_t *pick, uint8_t *out, uint32_t *file_len,
+                            uint32_t *status);
 
 struct Vp8In;
 // lossy WebP inputs (k_webp_dec.hip): every image's VP8 key frame -> RGB in the pixel pool; imgs[i].status = 0 or an error

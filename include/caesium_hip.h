@@ -233,7 +233,11 @@ int csp_batch_chunk_bits(csp_batch *b, size_t image, int trial, uint64_t *dst, s
  * 8-bit grey (channels 1), grey + alpha (2), RGB (3) or RGBA (4) pictures that are in device memory -> one VP8L file each (k_vp8l_enc.hip).
  * outputs / results as cs_batch_compress; returns the number of failed items.  cs_batch_compress (WebP sources) and cs_batch_convert (JPEG and PNG
  * sources) call it when p->webp_lossless is set; the lossy PNG -> WebP path calls it for the ALPH chunk of a transparent picture (channels 16 + n: the
- * last of n samples per pixel coded as a grey picture). */
+ * last of n samples per pixel coded as a grey picture).
+ * The coder is chosen by CSH_VP8L in the environment, read on EVERY call (so every caller above and the CLI inherit it): unset, empty or "plain" = literals
+ * only, the bytes oracle/png_oracle.c cso_vp8l_encode states; "refs" = the format's backward references and colour cache on top (k_vp8l_refs.hip), per picture
+ * never larger than the plain file (the smaller of the two streams is written); any other value fails every item with CS_ERR_UNSUPPORTED and a message that
+ * names the variable. */
 int csl_encode_pixels(const struct csp_pixels_s *sources, size_t count, int device, CByteArray *outputs, CCSResult *results);
 /* a lossy WebP file + its alpha plane coded by csl_encode_pixels (as a grey picture) -> the extended-format file with an ALPH chunk (VP8X, ALPH, VP8);
    lossy is replaced in place.  0 ok. */
