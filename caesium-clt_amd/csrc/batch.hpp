@@ -83,7 +83,11 @@ struct PixelPlan {
 };
 
 // a contiguous range of everything the coding kernels index: work items, slots, token chunks, tables, plans, list builder chunks, slot lists
-struct Stage { uint32_t work0 = 0, nwork = 0, slot0 = 0, nslots = 0, ech0 = 0, nech = 0, table0 = 0, ntables = 0, plan0 = 0, nplans = 0, nzc0 = 0, nnzc = 0, ls0 = 0, nls = 0, ts0 = 0, nts = 0; };
+struct Stage {
+    uint32_t work0 = 0, nwork = 0, slot0 = 0, nslots = 0, ech0 = 0, nech = 0, table0 = 0, ntables = 0, plan0 = 0, nplans = 0, nzc0 = 0, nnzc = 0, ls0 = 0, nls = 0, ts0 = 0, nts = 0;
+    // does some NzChunk of the stage ask for level 0 from the tiles (k_nzlist) / for a filtered level (k_nzfilter)?  [0]: as planned (EncodePlan::nzchunks), [1]: in a run whose forward-DCT kernels built lists (nzchunks_fused)
+    bool nz_build[2] = {true, true}, nz_filter[2] = {true, true};
+};
 struct SearchImg {
     int cand_work[64]; int ncand;       // candidate number -> work item (-1: not coded by itself -- see search_work)
     int Al_luma = 0, Al_chroma = 0;
@@ -118,6 +122,11 @@ struct EncodePlan {
     std::vector<uint32_t> nzset_built;    // per set: levels some stage's builder makes
     std::vector<int> nzset_comp, nzset_image;
     std::vector<NzChunk> nzchunks;        // the builder's grid, stage after stage
+    // the same grid for a run in which the forward-DCT kernels build the level-0 lists of the components that allow it (k_pixel.hip nzf_*; PlaneWork::nzset): those
+    // components' chunks without bit 0.  A run that does not come through the transform (the re-quantisation of size targeting) takes `nzchunks`
+    std::vector<NzChunk> nzchunks_fused;
+    uint32_t n_fused = 0;                 // components whose list the transform builds (csh_timing.n_fused_lists of a run that does)
+    uint32_t last_run_fused = 0;          // ... of the last run
     std::vector<uint32_t> nz_est, nz_worst; // per list: estimated / largest possible number of entries
     uint32_t nz_nrec = 0;                 // per-(list, chunk) records
     uint64_t nz_cap = 0;                  // pool capacity: the sum of the regions
@@ -162,7 +171,7 @@ struct EncodePlan {
     DevBuf<DevEncTable> d_tables;
     DevBuf<NzList> d_nzlists;
     DevBuf<NzSet> d_nzsets;
-    DevBuf<NzChunk> d_nzchunks;
+    DevBuf<NzChunk> d_nzchunks, d_nzchunks_fused;
     DevBuf<uint32_t> d_nz_pool, d_nz_cursor, d_nz_chunk_off, d_nz_chunk_cnt, d_list_slots, d_tok_slots;
 };
 
@@ -289,6 +298,7 @@ struct PlanSwitches {
     bool tr_sort = true;        // CSH_TR_SORT != "0"
     int prog_par = -1;          // CSH_PROG_PAR: 0, 1, or -1 for anything else
     bool fused_420 = true;      // CSH_NO_FUSED_420 unset
+    bool nz_fused = true;       // CSH_NZ_FUSED != "0": the forward-DCT kernels build the level-0 coefficient lists
     static PlanSwitches read();
 };
 

@@ -235,6 +235,7 @@ PlanSwitches PlanSwitches::read() {
     s.profile = penv && *penv ? penv : "mozjpeg";
     s.nz_once = !is("CSH_NZ_ONCE", "0");
     s.tr_sort = !is("CSH_TR_SORT", "0");
+    s.nz_fused = !is("CSH_NZ_FUSED", "0");
     const char *pp = getenv("CSH_PROG_PAR");
     s.prog_par = pp && !strcmp(pp, "0") ? 0 : (pp && !strcmp(pp, "1") ? 1 : -1);
     s.fused_420 = !getenv("CSH_NO_FUSED_420");
@@ -772,7 +773,7 @@ bool BatchPlanner::progressive_plan(const Item &it, const ImgDesc &im, int img_i
 // pixel work + planes
 void BatchPlanner::plane_work(ImgDesc &im, const JpegInfo &in, const JpegInfo &o, int img_index, bool resized) {
     for (int c = 0; c < in.ncomp; c++) {
-        PlaneWork w; w.image = img_index; w.comp = c;
+        PlaneWork w; w.image = img_index; w.comp = c; w.nzset = 0xFFFFFFFFu;   // (finish_descriptors names the set: the lists are planned behind the pixel work)
         w.up = resized ? up_desc(1, 1, 0) : up_desc(in.hmax / in.comp[c].h, in.vmax / in.comp[c].v, in.comp[c].comp_w);
         w.dn = dn_kind(o.hmax / o.comp[c].h, o.vmax / o.comp[c].v);
         // the layouts k_resample_plane takes keep its mode numbers (in: 0 full, 1 h2v2, 2 h2v1 by the up factors); every other one is CSH_MODE_ANY
@@ -1063,6 +1064,31 @@ void BatchPlanner::finish_descriptors() {
         for (ImgDesc &im : b->imgs) for (int c = 0; c < im.ncomp; c++) im.out[c].tile_base += b->ntiles_in;
     for (size_t i = 0; i < b->enc.plans.size(); i++) b->enc.plans[i].tile_base = b->imgs[size_t(b->enc.plan_image[i])].out[b->enc.plan_comp[i]].tile_base;
     for (size_t i = 0; i < b->enc.nzsets.size(); i++) b->enc.nzsets[i].tile_base = b->imgs[size_t(b->enc.nzset_image[i])].out[b->enc.nzset_comp[i]].tile_base;
+    {   // Which components' level-0 lists do the forward-DCT kernels build (k_pixel.hip nzf_*)?  Those whose real block grid is as wide as the padded one: a
+        // workgroup's 256 padded blocks are then the 256 real blocks of a list chunk.  Their chunks lose bit 0 in the grid such a run takes.  Not under the
+        // trellis quantiser without CSH_NZ_ONCE (or CSH_TR_SORT): the coding stages then build level 0 a second time, from the tiles the trellis rewrote.
+        b->enc.nzchunks_fused = b->enc.nzchunks;
+        const bool allowed = sw.nz_fused && !b->lossless && !b->webp && !b->rgb_out && !(b->tr.trellis && progressive && !b->tr.nz_once);
+        std::vector<uint8_t> fused(b->enc.nzsets.size(), 0);
+        for (PlaneWork &w : b->pix.pwork) {
+            const size_t at = size_t(w.image) * CSH_MAX_COMPS + size_t(w.comp);
+            const int si = allowed && at < b->enc.nzset_of.size() ? b->enc.nzset_of[at] : -1;
+            if (si < 0) continue;
+            const NzSet &S = b->enc.nzsets[size_t(si)];
+            if (S.real_bw != S.bw || S.list[0] == 0xFFFFFFFFu) continue;
+            w.nzset = uint32_t(si); fused[size_t(si)] = 1; b->enc.n_fused++;
+        }
+        for (NzChunk &ch : b->enc.nzchunks_fused) if (fused[ch.set]) ch.levels &= ~1u;
+        auto flags = [&](Stage &sg) {
+            for (int f = 0; f < 2; f++) {
+                const std::vector<NzChunk> &v = f ? b->enc.nzchunks_fused : b->enc.nzchunks;
+                sg.nz_build[f] = sg.nz_filter[f] = false;
+                for (uint32_t i = sg.nzc0; i < sg.nzc0 + sg.nnzc; i++) { sg.nz_build[f] |= (v[i].levels & 1u) != 0u; sg.nz_filter[f] |= (v[i].levels & ~1u) != 0u; }
+            }
+        };
+        for (Stage &sg : b->enc.stage) flags(sg);
+        flags(b->tr.tstage);
+    }
     for (ParScan &ps : b->dec.pscans)   // table selectors: slot numbers of the table-set form the batch uses
         for (int m = 0; m < ps.nb_mcu && m < 10; m++) {
             int dcs = ps.dct[m] & 3, acs = 4 + (ps.act[m] & 3);
@@ -1117,7 +1143,7 @@ int BatchPlanner::upload(Laps &laps) {
         b->enc.d_tok_off.alloc(4 * size_t(b->enc.nslots) + 4) || b->enc.d_chunk_ntok.alloc(4 * size_t(b->enc.nslots) + 4) || b->enc.d_slot_hist.alloc(size_t(b->enc.hist_rows) * 256 + 256) ||
         b->enc.d_slot_raw.alloc(size_t(b->enc.nslots) + 1) || b->enc.d_img_list.upload(b->enc.img_list, st) || b->enc.d_img_nlist.upload(b->enc.img_nlist, st) || b->enc.d_scan_cost.alloc(b->enc.swork.size() + 1) || b->enc.d_slot_eobh.alloc(16 * size_t(b->enc.nslots) + 16) || b->enc.d_chunk_bits.alloc(size_t(b->enc.nslots) + 1) || b->enc.d_chunk_off.alloc(size_t(b->enc.nslots) + 2) || b->enc.d_tok_cursor.alloc(b->enc.region_est.size() + 1) || b->enc.d_regions.upload(b->enc.regions, st) ||
         b->enc.d_tables.alloc(b->enc.ntables) || b->enc.d_scan_pad.alloc(b->enc.swork.size() + 1) ||
-        b->enc.d_nzlists.upload(b->enc.nzlists, st) || b->enc.d_nzsets.upload(b->enc.nzsets, st) || b->enc.d_nzchunks.upload(b->enc.nzchunks, st) || b->enc.d_list_slots.alloc(size_t(b->enc.nlist_slots) + 1) || b->enc.d_tok_slots.alloc(size_t(b->enc.ntok_slots) + 1) ||
+        b->enc.d_nzlists.upload(b->enc.nzlists, st) || b->enc.d_nzsets.upload(b->enc.nzsets, st) || b->enc.d_nzchunks.upload(b->enc.nzchunks, st) || (b->enc.n_fused && b->enc.d_nzchunks_fused.upload(b->enc.nzchunks_fused, st)) || b->enc.d_list_slots.alloc(size_t(b->enc.nlist_slots) + 1) || b->enc.d_tok_slots.alloc(size_t(b->enc.ntok_slots) + 1) ||
         b->enc.d_nz_cursor.alloc(b->enc.nzlists.size() + 1) || b->enc.d_nz_chunk_off.alloc(size_t(b->enc.nz_nrec) + 1) || b->enc.d_nz_chunk_cnt.alloc(size_t(b->enc.nz_nrec) + 1) ||
         b->enc.d_scan_raw_off.alloc(b->enc.swork.size() + 2) || b->out.d_img_size.alloc(b->nimg + 1) || b->out.d_img_size_pad.alloc(b->nimg + 1) ||
         b->out.d_img_off.alloc(b->nimg + 2) || b->out.d_status.alloc(b->nimg) || b->out.d_overflow.alloc(4))

@@ -71,6 +71,7 @@ struct Run {
     KernelMarks marks;
     uint64_t raw_chunks = 0;
     bool eobrun_cleared = false;   // the decode phase's store-less passes have cleared the encoder's EOBRUN array on the side (k_dec_dense clear_share)
+    bool fused = false;            // the forward-DCT kernels of this run built level-0 lists: the stages take the builder's grid without them (EncodePlan::nzchunks_fused)
     EncCtx c;
     AsmCtx a;
 
@@ -200,12 +201,23 @@ struct Run {
     int pixels() {
         const int nw = b->lossless ? 0 : int(b->pix.pwork.size());
         int16_t *rawp = ((b->retain_dct || b->tr.trellis) && !b->lossless) ? b->pix.d_dct_raw.p : nullptr;   // the trellis quantiser works from the unquantised DCT
-        launch_xform_direct(st, b->d_imgs.p, b->pix.d_pwork.p, nw, b->max_tiles, b->d_quants.p, b->d_coef.p, b->d_coef.p, rawp, b->ntiles_in, b->tr.dering);
+        // the level-0 coefficient lists of the components that allow it are built here (PlaneWork::nzset): what the kernels add to must be zero in front of them
+        NzFuse nzf;
+        memset(&nzf, 0, sizeof nzf);
+        fused = nw && b->enc.n_fused;
+        if (fused) {
+            if (b->enc.d_nz_cursor.zero(st) || b->enc.d_nz_chunk_cnt.zero(st)) return -1;
+            nzf.nzsets = b->enc.d_nzsets.p; nzf.nzlists = b->enc.d_nzlists.p; nzf.nz_pool = b->enc.d_nz_pool.p; nzf.nz_cursor = b->enc.d_nz_cursor.p;
+            nzf.nz_chunk_off = b->enc.d_nz_chunk_off.p; nzf.nz_chunk_cnt = b->enc.d_nz_chunk_cnt.p; nzf.overflow = b->out.d_overflow.p;
+            nzf.blk_cnt = (b->tr.trellis && b->tr.t_sort) ? b->tr.d_tblk_cnt.p : nullptr;
+            nzf.blk_off = (nzf.blk_cnt && b->tr.nz_once) ? b->tr.d_tblk_off.p : nullptr;
+        }
+        launch_xform_direct(st, b->d_imgs.p, b->pix.d_pwork.p, nw, b->max_tiles, b->d_quants.p, b->d_coef.p, b->d_coef.p, rawp, b->ntiles_in, b->tr.dering, nzf);
         MARK(KS_XFORM_DIRECT);
         launch_resample_plane(st, b->d_imgs.p, b->pix.d_pwork.p, nw, b->pix.max_quads, b->pix.d_planes.p, b->pix.d_oplanes.p);
         if (b->pix.any_layout) launch_resample_any(st, b->d_imgs.p, b->pix.d_pwork.p, nw, b->pix.max_quads, b->pix.d_planes.p, b->pix.d_oplanes.p);
-        launch_plane_fdct(st, b->d_imgs.p, b->pix.d_pwork.p, nw, b->max_tiles, b->d_quants.p, b->pix.d_oplanes.p, b->d_coef.p, rawp, b->ntiles_in, b->tr.dering);
-        launch_resample_fdct_420(st, b->d_imgs.p, b->pix.d_pwork.p, nw, b->max_tiles, b->d_quants.p, b->pix.d_planes.p, b->d_coef.p, rawp, b->ntiles_in, b->tr.dering);
+        launch_plane_fdct(st, b->d_imgs.p, b->pix.d_pwork.p, nw, b->max_tiles, b->d_quants.p, b->pix.d_oplanes.p, b->d_coef.p, rawp, b->ntiles_in, b->tr.dering, nzf);
+        launch_resample_fdct_420(st, b->d_imgs.p, b->pix.d_pwork.p, nw, b->max_tiles, b->d_quants.p, b->pix.d_planes.p, b->d_coef.p, rawp, b->ntiles_in, b->tr.dering, nzf);
         MARK(KS_RESAMPLE_FDCT);
         if (!b->lossless) launch_fix_dummy(st, b->d_imgs.p, nimg, b->max_dummy, b->d_coef.p);
         MARK(KS_FIX_DUMMY);
@@ -253,7 +265,7 @@ struct Run {
     int encode_begin() {
         fill_enc_ctx();
         launch_reset_works(st, b->enc.d_swork.p, c.nwork);
-        if (b->enc.d_nz_cursor.zero(st) || b->enc.d_nz_chunk_cnt.zero(st)) return -1;
+        if (!fused && (b->enc.d_nz_cursor.zero(st) || b->enc.d_nz_chunk_cnt.zero(st))) return -1;   // (a fused run: zeroed in front of the transform, which has added to them)
         if (b->enc.d_symbits.zero(st) || b->enc.d_eobbits.zero(st) || (!eobrun_cleared && b->enc.d_eobrun.zero(st)) || b->enc.d_tables.zero(st) || b->enc.d_tok_cursor.zero(st) || b->enc.d_slot_eobh.zero(st) || b->enc.d_scan_pad.zero(st)) return -1;
 #ifdef CSH_EMUL
         if (b->enc.d_raw.zero(st)) return -1;   // the emulation's packer ORs every word into the pool (no LDS window there)
@@ -266,7 +278,8 @@ struct Run {
 
     void set_stage(const Stage &sg) {
         c.echunks = b->enc.d_echunks.p + sg.ech0; c.nechunks = sg.nech; c.slot0 = sg.slot0; c.nslots = sg.nslots;
-        c.nzchunks = b->enc.d_nzchunks.p + sg.nzc0; c.nnzchunks = sg.nnzc;
+        c.nzchunks = (fused ? b->enc.d_nzchunks_fused.p : b->enc.d_nzchunks.p) + sg.nzc0; c.nnzchunks = sg.nnzc;
+        c.nz_build = sg.nz_build[fused ? 1 : 0]; c.nz_filter = sg.nz_filter[fused ? 1 : 0];
         c.list_slots = b->enc.d_list_slots.p + sg.ls0; c.nlist_slots = sg.nls; c.tok_slots = b->enc.d_tok_slots.p + sg.ts0; c.ntok_slots = sg.nts;
     }
 
@@ -420,6 +433,7 @@ struct Run {
 
 int run_once(csh_batch *b, csh_timing *t, bool requant_only) {
     Run r(b, t);
+    b->enc.last_run_fused = 0;
     if (r.pools() || r.marks.start()) return -1;
     // a re-run at another quality (size targeting): from the retained DCT -- unless the batch derings: the overshoot mozjpeg's deringing allows
     // depends on the DC quantiser (jcdctmgr.c preprocess_deringing), so the forward DCT's input changes with the table and the re-run starts
@@ -435,6 +449,7 @@ int run_once(csh_batch *b, csh_timing *t, bool requant_only) {
         if (r.pixels()) return -1;
     }
     if (r.encode_begin()) return -1;
+    b->enc.last_run_fused = r.fused ? b->enc.n_fused : 0u;
     if (b->tr.trellis ? r.trellis() : r.marks.skip_to(KS_NZLIST)) return -1;
     r.fill_asm_ctx();
     if (r.stage(b->enc.stage[0], true, false)) return -1;

@@ -467,8 +467,8 @@ __global__ void k_reset_works(ScanWork *work, int nwork) {
 
 void launch_nzlist(hipStream_t st, const EncCtx &c) {
     if (!c.nnzchunks) return;
-    CSH_LAUNCH_PHASED(k_nzlist, 3, dim3(c.nnzchunks), dim3(2 * CSP_WAVE_THREADS), st, c);
-    CSH_LAUNCH(k_nzfilter, dim3(c.nnzchunks), dim3(CSP_WAVE_THREADS), st, c);
+    if (c.nz_build) CSH_LAUNCH_PHASED(k_nzlist, 3, dim3(c.nnzchunks), dim3(2 * CSP_WAVE_THREADS), st, c);
+    if (c.nz_filter) CSH_LAUNCH(k_nzfilter, dim3(c.nnzchunks), dim3(CSP_WAVE_THREADS), st, c);
 }
 void launch_list_stats(hipStream_t st, const EncCtx &c) { if (c.nlist_slots) CSH_LAUNCH(k_list_stats, dim3((c.nlist_slots + 3) / 4), dim3(4 * CSP_WAVE_THREADS), st, c); }
 void launch_list_pack(hipStream_t st, const EncCtx &c) { if (c.nlist_slots) CSH_LAUNCH(k_list_pack, dim3((c.nlist_slots + 3) / 4), dim3(4 * CSP_WAVE_THREADS), st, c); }

@@ -17,6 +17,9 @@
 #include <utility>
 
 #include "kernels.h"
+#ifndef CSH_EMUL
+#include "wave.h"
+#endif
 
 namespace csh {
 
@@ -179,18 +182,24 @@ template <int K>
 __device__ __forceinline__ static uint32_t quant_one(const int x[64], const DevQuant &q) {
     return float_bits(__builtin_fmaf(float(x[kZ2N[K]]), q.rcp[K], 12582912.0f));   // low half = the level
 }
+// lv: the block's levels as they are stored, octet by octet -- what the list builder below (nzf_*) works from
 template <int J>
-__device__ __forceinline__ static void quant_store_octet(const int x[64], const DevQuant &q, int16_t *__restrict__ blk) {
-    uint4 v;
+__device__ __forceinline__ static void quant_store_octet(const int x[64], const DevQuant &q, int16_t *__restrict__ blk /* of octet J & ~3 */, uint4 &v) {
     v.x = pack_halves(quant_one<8 * J + 0>(x, q), quant_one<8 * J + 1>(x, q));
     v.y = pack_halves(quant_one<8 * J + 2>(x, q), quant_one<8 * J + 3>(x, q));
     v.z = pack_halves(quant_one<8 * J + 4>(x, q), quant_one<8 * J + 5>(x, q));
     v.w = pack_halves(quant_one<8 * J + 6>(x, q), quant_one<8 * J + 7>(x, q));
-    nt_store16(blk + CSH_OCT_STRIDE * J, v);
+    nt_store16(blk + CSH_OCT_STRIDE * (J & 3), v);
 }
 template <int... J>
-__device__ __forceinline__ static void quant_store_all(const int x[64], const DevQuant &q, int16_t *__restrict__ blk, std::integer_sequence<int, J...>) {
-    ((quant_store_octet<J>(x, q, blk), CSH_SCHED_FENCE()), ...);
+__device__ __forceinline__ static void quant_store_all(const int x[64], const DevQuant &q, int16_t *__restrict__ blk, uint4 lv[8], std::integer_sequence<int, J...>) {
+    // The eight stores of a block are 1 KiB apart and a store's immediate offset ends at 4 KiB: octets 4..7 get a base of their own, made HERE.  (Left to itself the
+    // compiler makes four more 64-bit addresses at the top of the kernel and carries them through the whole transform: eight registers the levels' stay in lv needs.)
+    int16_t *hi = blk + 4 * CSH_OCT_STRIDE;
+#ifndef CSH_EMUL
+    asm volatile("" : "+v"(hi));
+#endif
+    ((quant_store_octet<J>(x, q, J < 4 ? blk : hi, lv[J]), CSH_SCHED_FENCE()), ...);
 }
 template <int J>
 __device__ __forceinline__ static void raw_store_octet(const int x[64], int16_t *__restrict__ raw) {
@@ -407,9 +416,12 @@ __device__ __forceinline__ static void dering_block_pk(uint32_t pr[8][4], int dc
         pr[r][0] = pack_halves(at(0), at(1)); pr[r][1] = pack_halves(at(7), at(6)); pr[r][2] = pack_halves(at(2), at(3)); pr[r][3] = pack_halves(at(5), at(4));
     }
 }
+// where block b of a component goes: its tile in the coefficient pool and, if the unquantised DCT is retained (dct_raw not null), its place there.  The two addresses
+// are made where they are used, behind the transform, from the block number: made at the top of the kernel they are four registers carried through all of it
+struct BlkOut { int16_t *coef_out; uint32_t tile_base; int b; int16_t *dct_raw; uint32_t raw_tile_base; };
 // packed rows -> [deringing] -> 2-D FDCT -> [retained DCT] -> quantise -> store
 template <bool DERING, bool CENTRED>
-__device__ __forceinline__ static void fdct_quant_store_pk(uint32_t pr[8][4], const DevQuant &q, int16_t *__restrict__ blk, int16_t *__restrict__ raw, CSH_DERING_LDS) {
+__device__ __forceinline__ static void fdct_quant_store_pk(uint32_t pr[8][4], const DevQuant &q, const BlkOut &o, uint4 lv[8], CSH_DERING_LDS) {
     CSH_SCHED_FENCE();
     if (DERING) { dering_block_pk<CENTRED>(pr, int(q.q[0]), dr_col); CSH_SCHED_FENCE(); }
     int x[64];
@@ -428,10 +440,12 @@ __device__ __forceinline__ static void fdct_quant_store_pk(uint32_t pr[8][4], co
         fdct1d_pk<false>(A, B, C, D, R2, (c == 0 && !CENTRED) ? RDC : TWO, TWO, x[c], x[8 + c], x[16 + c], x[24 + c], x[32 + c], x[40 + c], x[48 + c], x[56 + c]);
     }
     CSH_SCHED_FENCE();
-    if (raw) {   // size-targeting keeps the unquantised DCT so later tries only re-quantise; the trellis quantiser works from it
-        if (CSH_RAW_VIA_LDS) raw_put_all(x, dr_col, int(threadIdx.x), Oct()); else raw_store_all(x, raw, Oct());
+    int b = o.b;
+    CSH_PIN(b);
+    if (o.dct_raw) {   // size-targeting keeps the unquantised DCT so later tries only re-quantise; the trellis quantiser works from it
+        if (CSH_RAW_VIA_LDS) raw_put_all(x, dr_col, int(threadIdx.x), Oct()); else raw_store_all(x, o.dct_raw + raw_index(o.raw_tile_base, b), Oct());
     }
-    quant_store_all(x, q, blk, Oct());
+    quant_store_all(x, q, o.coef_out + coef_index(o.tile_base, b, 0), lv, Oct());
 }
 // centred samples in registers (natural order) -> the packed rows
 __device__ __forceinline__ static void pack_rows(const int x[64], uint32_t pr[8][4]) {
@@ -442,10 +456,16 @@ __device__ __forceinline__ static void pack_rows(const int x[64], uint32_t pr[8]
     }
 }
 template <bool DERING, bool CENTRED = false>
-__device__ __forceinline__ static void fdct_quant_store(int x[64], const DevQuant &q, int16_t *__restrict__ blk, int16_t *__restrict__ raw, CSH_DERING_LDS) {
+__device__ __forceinline__ static void fdct_quant_store(int x[64], const DevQuant &q, const BlkOut &o, uint4 lv[8], CSH_DERING_LDS) {
     uint32_t pr[8][4];
     pack_rows(x, pr);
-    fdct_quant_store_pk<DERING, CENTRED>(pr, q, blk, raw, dr_col);
+    fdct_quant_store_pk<DERING, CENTRED>(pr, q, o, lv, dr_col);
+}
+// the same with the block's two addresses given and the levels not wanted: the form tests/xform_block_check.cpp drives
+template <bool DERING, bool CENTRED = false>
+__device__ __forceinline__ static void fdct_quant_store(int x[64], const DevQuant &q, int16_t *__restrict__ blk, int16_t *__restrict__ raw, CSH_DERING_LDS) {
+    uint4 lv[8];
+    fdct_quant_store<DERING, CENTRED>(x, q, BlkOut{blk, 0u, 0, raw, 0u}, lv, dr_col);
 }
 
 // re-quantise a retained DCT block with another table (k_requant)
@@ -458,7 +478,8 @@ __device__ __forceinline__ static void requant_block(const int16_t *__restrict__
     const uint4 v[8] = {*reinterpret_cast<const uint4 *>(raw + CSH_RAW_OCT * J)...};
     int x[64];
     (raw_to_nat<J>(x, v[J], Oct()), ...);
-    quant_store_all(x, q, blk, Oct());
+    uint4 lv[8];
+    quant_store_all(x, q, blk, lv, Oct());
 }
 
 __device__ __forceinline__ static void store_zero_block(int16_t *__restrict__ blk) {
@@ -468,11 +489,156 @@ __device__ __forceinline__ static void store_zero_block(int16_t *__restrict__ bl
 }
 
 // ------------------------------------------------------------------------------------------------
+// The level-0 coefficient list of a component (types.h NzList), built by the kernel that has just quantised it: k_nzlist (k_aclist.hip) reads every
+// tile of the batch again to write down what the lanes here hold in registers.  Where the component's real width is its padded width
+// (PlaneWork::nzset; batch_plan.cpp), the 256 blocks of workgroup j ARE chunk j of the list, in list order, one block per lane.  Behind the
+// transform (phase 0 of the kernel) every lane counts its entries -- its non-zero AC levels and one END -- and then
+//   phase 1  a wave scan places the lanes; every lane walks its levels in zig-zag order and puts its entries into the wave's stretch of LDS
+//            (s_dr, free by then; a level that is zero is stored too, where the next entry or the END overwrites it: no branch per coefficient);
+//   phase 2  one lane reserves the chunk's room with ONE atomic add on the list's cursor and writes the chunk's record, as k_nzlist does;
+//   phase 3  every wave copies its stretch out with contiguous stores; the per-block counts and offsets the trellis stage asks for.
+// A wave whose blocks hold more entries than its stretch (dense blocks: noise, q 98+) walks its levels again in phase 3, straight to memory.
+// The entries, their order and the records are k_nzlist's; only where a chunk lands in its list's region depends on the order of the atomics, as there.
+#define CSH_NZF_CAP 2040u                  // entries of a wave's stretch: s_dr as 8192 words = 4 stretches + the control words
+#define CSH_NZF_CTL (4u * CSH_NZF_CAP)     // words [0..3]: the waves' totals; [4]: the chunk's first entry relative to the list's region, 0xFFFFFFFF: no room
+#define CSH_NZF_PHASES 4
+__device__ __forceinline__ static uint32_t nzf_ones(uint32_t w, uint32_t ones) {   // 1 in every 16-bit half of w that is not zero; ones: 0x00010001
+#ifdef CSH_EMUL
+    (void)ones;
+    return ((w & 0xFFFFu) ? 1u : 0u) | ((w >> 16) ? 0x10000u : 0u);
+#else
+    uint32_t r;   // (as the builtin the compiler turns the minimum into two compares, two selects and a v_perm per word)
+    asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(w), "v"(ones));
+    return r;
+#endif
+}
+__device__ __forceinline__ static uint32_t nzf_count(const uint4 lv[8]) {   // non-zero AC levels of the block
+    uint32_t ones = 0x00010001u;
+    CSH_PIN(ones);
+    uint32_t s = 0;
+    CSH_UNROLL
+    for (int j = 0; j < 8; j++) { s += nzf_ones(lv[j].x, ones); s += nzf_ones(lv[j].y, ones); s += nzf_ones(lv[j].z, ones); s += nzf_ones(lv[j].w, ones); }
+    s -= nzf_ones(lv[0].x, ones) & 1u;   // the DC level
+    return (s & 0xFFFFu) + (s >> 16);
+}
+template <int K>
+__device__ __forceinline__ static void nzf_put(uint32_t w, uint32_t kb, uint32_t *dst, uint32_t &o) {
+    const int h = (K & 1) ? (int(w) >> 16) : (int(w << 16) >> 16);
+    const uint32_t a = uint32_t(h < 0 ? -h : h);   // (a level of the scalar quantiser is at most 2^15 / 8: k_nzlist's guard against -32768 has nothing to do here)
+    dst[o] = (kb | uint32_t(K)) | (h < 0 ? 128u : 0u) | (a << 8);
+    o += h != 0 ? 1u : 0u;
+}
+template <int J>
+__device__ __forceinline__ static void nzf_octet(const uint4 &v, uint32_t kb, uint32_t *dst, uint32_t &o) {
+    uint32_t x = v.x, y = v.y, z = v.z, w = v.w;
+    if ((x | y | z | w) == 0u) return;   // (high octets are zero in most blocks: a wave none of whose lanes has one skips the eight steps)
+    // the entries are made HERE, octet by octet: left to itself the compiler makes all 63 of them (and their flags) in front of the walk, for both walks at once -- 167 registers
+    CSH_PIN(x); CSH_PIN(y); CSH_PIN(z); CSH_PIN(w);
+    if (J) nzf_put<8 * J>(x, kb, dst, o);
+    nzf_put<8 * J + 1>(x, kb, dst, o); nzf_put<8 * J + 2>(y, kb, dst, o); nzf_put<8 * J + 3>(y, kb, dst, o); nzf_put<8 * J + 4>(z, kb, dst, o);
+    nzf_put<8 * J + 5>(z, kb, dst, o); nzf_put<8 * J + 6>(w, kb, dst, o); nzf_put<8 * J + 7>(w, kb, dst, o);
+}
+// the entries of block `blk` of the chunk to dst[o ..]: at most dst[o + its count - 1], the END's place, is touched
+template <int... J>
+__device__ __forceinline__ static void nzf_walk(const uint4 lv[8], uint32_t blk, bool real, uint32_t *dst, uint32_t o, std::integer_sequence<int, J...>) {
+    if (!real) return;   // (lv is whatever it was: the lane had no block to transform)
+    const uint32_t kb = blk << 23;
+    ((nzf_octet<J>(lv[J], kb, dst, o), CSH_SCHED_FENCE()), ...);
+    dst[o] = CSH_NZ_END | kb;
+}
+// does this workgroup build a chunk?  (workgroup-uniform)
+__device__ __forceinline__ static bool nzf_begin(const NzFuse &f, const PlaneWork &w, NzSet &S) {
+    if (!f.nz_pool || w.nzset == 0xFFFFFFFFu) return false;
+    S = f.nzsets[w.nzset];
+    return blockIdx.x * 256u < S.nunits;
+}
+// end of phase 0: ns[0] = the lane's entries (a lane without a real block has none, and nothing looks at its lv)
+__device__ __forceinline__ static void nzf_counted(const NzSet &S, const uint4 lv[8], uint32_t ns[2], uint32_t *cnt_lds) {
+    const uint32_t u = blockIdx.x * 256u + threadIdx.x;
+    ns[0] = u < S.nunits ? nzf_count(lv) + 1u : 0u;
+#ifdef CSH_EMUL
+    cnt_lds[threadIdx.x] = ns[0];   // the emulation's lanes run one after the other: the scan of phase 1 is a sum over these
+#else
+    (void)cnt_lds;
+#endif
+}
+__device__ __forceinline__ static void nzf_phase(int phase, const NzFuse &f, const NzSet &S, const uint4 lv[8], uint32_t ns[2], uint32_t *lds, const uint32_t *cnt_lds) {
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u, u = blockIdx.x * 256u + tid;
+    const bool real = u < S.nunits;
+    if (phase == 1) {
+        uint32_t ex = 0, tot = 0;
+#ifdef CSH_EMUL
+        for (uint32_t i = 0; i < 64; i++) { const uint32_t n = cnt_lds[wave * 64u + i]; if (i < lane) ex += n; tot += n; }
+#else
+        (void)cnt_lds;
+        LV<uint32_t> c; c.v = ns[0];
+        ex = lscan(c, tot).v;
+#endif
+        ns[1] = ex;
+        if (lane == 0) lds[CSH_NZF_CTL + wave] = tot;
+        if (tot <= CSH_NZF_CAP) nzf_walk(lv, tid, real, lds + wave * CSH_NZF_CAP, ex, Oct());
+        return;
+    }
+    if (phase == 2) {
+        if (tid == 0) {
+            const NzList L0 = f.nzlists[S.list[0]];
+            const uint32_t n0 = lds[CSH_NZF_CTL] + lds[CSH_NZF_CTL + 1] + lds[CSH_NZF_CTL + 2] + lds[CSH_NZF_CTL + 3], n0a = (n0 + 3u) & ~3u, rec0 = L0.chunk0 + blockIdx.x;
+            const uint32_t rel = atomicAdd(&f.nz_cursor[S.list[0]], n0a);
+            const bool ok0 = uint64_t(rel) + n0a <= L0.cap;
+            f.nz_chunk_off[rec0] = rel; f.nz_chunk_cnt[rec0] = ok0 ? n0 : 0u;
+            if (!ok0) f.overflow[1] = 1;
+            lds[CSH_NZF_CTL + 4] = ok0 ? rel : 0xFFFFFFFFu;
+        }
+        return;
+    }
+    const uint32_t rel = lds[CSH_NZF_CTL + 4];
+    if (rel == 0xFFFFFFFFu) return;
+    const uint32_t t0 = lds[CSH_NZF_CTL], t1 = lds[CSH_NZF_CTL + 1], t2 = lds[CSH_NZF_CTL + 2], t3 = lds[CSH_NZF_CTL + 3];
+    const uint32_t wbase = uint32_t(CSH_UNIFORM((wave > 0 ? t0 : 0u) + (wave > 1 ? t1 : 0u) + (wave > 2 ? t2 : 0u)));
+    const uint32_t tot = uint32_t(CSH_UNIFORM(wave == 0 ? t0 : wave == 1 ? t1 : wave == 2 ? t2 : t3)), n0 = t0 + t1 + t2 + t3;
+    uint32_t *chunk = f.nz_pool + f.nzlists[S.list[0]].base + rel;
+    if (tot <= CSH_NZF_CAP) {
+        const uint32_t *src = lds + wave * CSH_NZF_CAP;
+        for (uint32_t i = lane; i < tot; i += 64u) chunk[wbase + i] = src[i];
+    } else {
+        nzf_walk(lv, tid, real, chunk + wbase, ns[1], Oct());
+    }
+    if (real && f.blk_cnt && S.cnt_base != 0xFFFFFFFFu) {   // what k_trellis_sort and k_trellis_ac's write-back take from the statistics stage's builder
+        f.blk_cnt[S.cnt_base + u] = uint8_t(ns[0] - 1u);
+        if (f.blk_off) f.blk_off[S.cnt_base + u] = uint16_t(wbase + ns[1]);   // (a chunk holds at most 256 x 64 entries)
+    }
+    if (wave == 3u && n0 + lane < ((n0 + 3u) & ~3u)) chunk[n0 + lane] = 0u;   // padding to the next 16-byte boundary: entries that code nothing
+}
+// How a kernel carries the phases.  The emulation re-enters it once per phase and lane (gpu_rt.h CSH_PHASE_LOOP): the transform is the loop's phase 0, the
+// others go to nzf_phase.  On the device the kernel is straight-line code -- a run-time loop around the transform keeps the allocator from the 128
+// registers it fits otherwise -- : the loop below is its phase 0 only, and the three list phases follow it behind a barrier each (every lane of the
+// workgroup comes here: lanes without a block leave the transform by `break`, and `fuse` is workgroup-uniform).
+#ifdef CSH_EMUL
+#define CSH_NZF_STATE CSH_SHARED uint32_t s_nzc[256]; CSH_PERSIST(uint4, lv, 8); CSH_PERSIST(uint32_t, ns, 2)
+#define CSH_NZF_LOOP CSH_PHASE_LOOP(CSH_NZF_PHASES)
+#define CSH_NZF_EARLY(x) x   // every phase asks whether the workgroup builds a chunk
+#define CSH_NZF_LATE(x) ((void)0)
+#define CSH_NZF_FINISH() ((void)0)
+#else
+#define CSH_NZF_STATE uint32_t *const s_nzc = nullptr; uint4 lv[8]; uint32_t ns[2] = {0u, 0u}
+#define CSH_NZF_LOOP for (int phase = 0, once_ = 1; once_; once_ = 0)
+#define CSH_NZF_EARLY(x) ((void)0)
+#define CSH_NZF_LATE(x) x    // ... behind the transform: the set's descriptor does not sit in registers through it
+#define CSH_NZF_FINISH()                                                                                                                  \
+    do {                                                                                                                                   \
+        if (!fuse) return;                                                                                                                 \
+        CSH_UNROLL                                                                                                                         \
+        for (int ph_ = 1; ph_ < CSH_NZF_PHASES; ph_++) { __syncthreads(); nzf_phase(ph_, nzf, S, lv, ns, reinterpret_cast<uint32_t *>(&s_dr[0][0]), s_nzc); } \
+    } while (0)
+#endif
+
+// ------------------------------------------------------------------------------------------------
 // mode 0: full-resolution component, IDCT -> (crop + edge expand) -> FDCT -> quantise
 template <bool DERING>
 __global__ void __launch_bounds__(256) k_xform_direct(const ImgDesc *__restrict__ imgs, const PlaneWork *__restrict__ work, const DevQuant *__restrict__ quant,
-                                                       const int16_t *__restrict__ coef_in, int16_t *__restrict__ coef_out, int16_t *__restrict__ dct_raw, uint32_t raw_tile0) {
-    CSH_SHARED int16_t s_dr[64][256];   // deringing: a column per lane; then the wave's columns carry its retained-DCT blocks to whole-line stores (raw_copy_out)
+                                                       const int16_t *__restrict__ coef_in, int16_t *__restrict__ coef_out, int16_t *__restrict__ dct_raw, uint32_t raw_tile0, NzFuse nzf) {
+    CSH_SHARED int16_t s_dr[64][256];   // deringing: a column per lane; then the wave's columns carry its retained-DCT blocks to whole-line stores (raw_copy_out); then the list's entries (nzf_phase)
+    CSH_NZF_STATE;
     const PlaneWork w = work[blockIdx.y];
     if (w.mode != 0) return;
     const ImgDesc &im = imgs[w.image];
@@ -480,20 +646,32 @@ __global__ void __launch_bounds__(256) k_xform_direct(const ImgDesc *__restrict_
     int tile = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     int lane = threadIdx.x & 63;
     int b = tile * 64 + lane;
+    NzSet S;
+    bool fuse = false;
+    CSH_NZF_EARLY(fuse = nzf_begin(nzf, w, S));
+    CSH_NZF_LOOP {
+    if (phase) {   // (the transform is phase 0; a workgroup that builds no list is through with it)
+        if (!fuse) break;
+        nzf_phase(phase, nzf, S, lv, ns, reinterpret_cast<uint32_t *>(&s_dr[0][0]), s_nzc);
+        continue;
+    }
     bool has_raw = false;
     do {
         if (b >= go.bw * go.bh) break;
         int by = b / go.bw, bx = b - by * go.bw;
-        int16_t *dst = coef_out + coef_index(go.tile_base, b, 0);
-        if (by >= go.real_bh || bx >= go.real_bw) { store_zero_block(dst); break; }
+        if (by >= go.real_bh || bx >= go.real_bw) { store_zero_block(coef_out + coef_index(go.tile_base, b, 0)); break; }
         int x[64];
         load_idct<true>(coef_in + coef_index(gi.tile_base, by * gi.bw + bx, 0), quant[CSH_UNIFORM(im.qt_in[w.comp])], x);
         int vc = gi.comp_w - bx * 8, vr = gi.comp_h - by * 8;
         if (vc < 8 || vr < 8) replicate_edges(x, vc, vr);
-        fdct_quant_store<DERING, true>(x, quant[CSH_UNIFORM(im.qt_out[w.comp])], dst, dct_raw ? dct_raw + raw_index(go.tile_base - raw_tile0, b) : nullptr, s_dr);
+        fdct_quant_store<DERING, true>(x, quant[CSH_UNIFORM(im.qt_out[w.comp])], BlkOut{coef_out, go.tile_base, b, dct_raw, go.tile_base - raw_tile0}, lv, s_dr);
         has_raw = dct_raw != nullptr;
     } while (0);
     if (dct_raw) raw_copy_out(dct_raw + raw_index(go.tile_base - raw_tile0, tile * 64), has_raw, s_dr, int(threadIdx.x));
+    CSH_NZF_LATE(fuse = nzf_begin(nzf, w, S));
+    if (fuse) nzf_counted(S, lv, ns, s_nzc);
+    }
+    CSH_NZF_FINISH();
 }
 
 // mode 1 producer: subsampled component, IDCT -> u8 plane (pitch real_bw*8, rows real_bh*8, edges replicated)
@@ -773,8 +951,9 @@ __global__ void __launch_bounds__(256) k_resample_any(const ImgDesc *imgs, const
 // encoder-side plane -> FDCT -> quantise, one block per lane
 template <bool DERING>
 __global__ void __launch_bounds__(256) k_plane_fdct(const ImgDesc *__restrict__ imgs, const PlaneWork *__restrict__ work, const DevQuant *__restrict__ quant, const uint8_t *__restrict__ oplanes,
-                                                     int16_t *__restrict__ coef_out, int16_t *__restrict__ dct_raw, uint32_t raw_tile0) {
-    CSH_SHARED int16_t s_dr[64][256];   // deringing: a column per lane; then the wave's columns carry its retained-DCT blocks to whole-line stores (raw_copy_out)
+                                                     int16_t *__restrict__ coef_out, int16_t *__restrict__ dct_raw, uint32_t raw_tile0, NzFuse nzf) {
+    CSH_SHARED int16_t s_dr[64][256];   // deringing: a column per lane; then the wave's columns carry its retained-DCT blocks to whole-line stores (raw_copy_out); then the list's entries (nzf_phase)
+    CSH_NZF_STATE;
     const PlaneWork w = work[blockIdx.y];
     if (w.mode == 0 || w.mode == 10) return;
     const ImgDesc &im = imgs[w.image];
@@ -782,12 +961,20 @@ __global__ void __launch_bounds__(256) k_plane_fdct(const ImgDesc *__restrict__ 
     int tile = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     int lane = threadIdx.x & 63;
     int b = tile * 64 + lane;
+    NzSet S;
+    bool fuse = false;
+    CSH_NZF_EARLY(fuse = nzf_begin(nzf, w, S));
+    CSH_NZF_LOOP {
+    if (phase) {
+        if (!fuse) break;
+        nzf_phase(phase, nzf, S, lv, ns, reinterpret_cast<uint32_t *>(&s_dr[0][0]), s_nzc);
+        continue;
+    }
     bool has_raw = false;
     do {
     if (b >= go.bw * go.bh) break;
     int by = b / go.bw, bx = b - by * go.bw;
-    int16_t *dst = coef_out + coef_index(go.tile_base, b, 0);
-    if (by >= go.real_bh || bx >= go.real_bw) { store_zero_block(dst); break; }
+    if (by >= go.real_bh || bx >= go.real_bw) { store_zero_block(coef_out + coef_index(go.tile_base, b, 0)); break; }
     const int pitch = go.real_bw * 8;
     const uint8_t *p = oplanes + im.oplane_off[w.comp] + size_t(by * 8) * pitch + bx * 8;
     uint32_t pr[8][4];
@@ -796,10 +983,14 @@ __global__ void __launch_bounds__(256) k_plane_fdct(const ImgDesc *__restrict__ 
         const uint2 v = *reinterpret_cast<const uint2 *>(p + size_t(r) * pitch);
         pr[r][0] = bytes_to_halves<0, 1>(v.x); pr[r][2] = bytes_to_halves<2, 3>(v.x); pr[r][1] = bytes_to_halves<3, 2>(v.y); pr[r][3] = bytes_to_halves<1, 0>(v.y);
     }
-    fdct_quant_store_pk<DERING, false>(pr, quant[CSH_UNIFORM(im.qt_out[w.comp])], dst, dct_raw ? dct_raw + raw_index(go.tile_base - raw_tile0, b) : nullptr, s_dr);
+    fdct_quant_store_pk<DERING, false>(pr, quant[CSH_UNIFORM(im.qt_out[w.comp])], BlkOut{coef_out, go.tile_base, b, dct_raw, go.tile_base - raw_tile0}, lv, s_dr);
     has_raw = dct_raw != nullptr;
     } while (0);
     if (dct_raw) raw_copy_out(dct_raw + raw_index(go.tile_base - raw_tile0, tile * 64), has_raw, s_dr, int(threadIdx.x));
+    CSH_NZF_LATE(fuse = nzf_begin(nzf, w, S));
+    if (fuse) nzf_counted(S, lv, ns, s_nzc);
+    }
+    CSH_NZF_FINISH();
 }
 
 // sixteen bytes of a plane row from a 4-byte aligned address (x0 - 4): one global_load_dwordx4
@@ -824,8 +1015,9 @@ __device__ __forceinline__ static Row16 load_row16(const uint8_t *p) {
 //            holds plane column (W-1)/2 (always the last block column).
 template <bool DERING>
 __global__ void __launch_bounds__(256) k_resample_fdct_420(const ImgDesc *__restrict__ imgs, const PlaneWork *__restrict__ work, const DevQuant *__restrict__ quant, const uint8_t *__restrict__ planes,
-                                                            int16_t *__restrict__ coef_out, int16_t *__restrict__ dct_raw, uint32_t raw_tile0) {
-    CSH_SHARED int16_t s_dr[64][256];   // deringing: a column per lane; then the wave's columns carry its retained-DCT blocks to whole-line stores (raw_copy_out)
+                                                            int16_t *__restrict__ coef_out, int16_t *__restrict__ dct_raw, uint32_t raw_tile0, NzFuse nzf) {
+    CSH_SHARED int16_t s_dr[64][256];   // deringing: a column per lane; then the wave's columns carry its retained-DCT blocks to whole-line stores (raw_copy_out); then the list's entries (nzf_phase)
+    CSH_NZF_STATE;
     const PlaneWork w = work[blockIdx.y];
     if (w.mode != 10) return;
     const ImgDesc &im = imgs[w.image];
@@ -833,12 +1025,20 @@ __global__ void __launch_bounds__(256) k_resample_fdct_420(const ImgDesc *__rest
     int tile = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     int lane = threadIdx.x & 63;
     int b = tile * 64 + lane;
+    NzSet S;
+    bool fuse = false;
+    CSH_NZF_EARLY(fuse = nzf_begin(nzf, w, S));
+    CSH_NZF_LOOP {
+    if (phase) {
+        if (!fuse) break;
+        nzf_phase(phase, nzf, S, lv, ns, reinterpret_cast<uint32_t *>(&s_dr[0][0]), s_nzc);
+        continue;
+    }
     bool has_raw = false;
     do {
     if (b >= go.bw * go.bh) break;
     int by = b / go.bw, bx = b - by * go.bw;
-    int16_t *dst = coef_out + coef_index(go.tile_base, b, 0);
-    if (by >= go.real_bh || bx >= go.real_bw) { store_zero_block(dst); break; }
+    if (by >= go.real_bh || bx >= go.real_bw) { store_zero_block(coef_out + coef_index(go.tile_base, b, 0)); break; }
     const int pitch = gi.real_bw * 8, rows_alloc = gi.real_bh * 8;
     const uint8_t *pl = planes + im.splane_off[w.comp];
     const int x0 = bx * 8, y0 = by * 8, W = im.enc_w, H = im.enc_h, och = go.comp_h;
@@ -922,10 +1122,14 @@ __global__ void __launch_bounds__(256) k_resample_fdct_420(const ImgDesc *__rest
                 for (int cc = 0; cc < 4; cc++) pr[r][cc] = pr[r - 1][cc];
             }
     }
-    fdct_quant_store_pk<DERING, false>(pr, quant[CSH_UNIFORM(im.qt_out[w.comp])], dst, dct_raw ? dct_raw + raw_index(go.tile_base - raw_tile0, b) : nullptr, s_dr);
+    fdct_quant_store_pk<DERING, false>(pr, quant[CSH_UNIFORM(im.qt_out[w.comp])], BlkOut{coef_out, go.tile_base, b, dct_raw, go.tile_base - raw_tile0}, lv, s_dr);
     has_raw = dct_raw != nullptr;
     } while (0);
     if (dct_raw) raw_copy_out(dct_raw + raw_index(go.tile_base - raw_tile0, tile * 64), has_raw, s_dr, int(threadIdx.x));
+    CSH_NZF_LATE(fuse = nzf_begin(nzf, w, S));
+    if (fuse) nzf_counted(S, lv, ns, s_nzc);
+    }
+    CSH_NZF_FINISH();
 }
 
 // size-targeting: re-quantise every retained DCT block with the image's CURRENT output table (one block per lane)
@@ -969,10 +1173,10 @@ __global__ void k_fix_dummy(const ImgDesc *imgs, int nimg, int16_t *coef_out) {
 static dim3 tile_grid(int max_tiles, int nwork) { return dim3((max_tiles + 3) / 4, nwork); }
 
 void launch_xform_direct(hipStream_t st, const ImgDesc *imgs, const PlaneWork *work, int nwork, int max_tiles, const DevQuant *quant,
-                         const int16_t *coef_in, int16_t *coef_out, int16_t *dct_raw, uint32_t raw_tile0, bool dering) {
+                         const int16_t *coef_in, int16_t *coef_out, int16_t *dct_raw, uint32_t raw_tile0, bool dering, const NzFuse &nzf) {
     if (!nwork) return;
-    if (dering) CSH_LAUNCH(k_xform_direct<true>, tile_grid(max_tiles, nwork), dim3(256), st, imgs, work, quant, coef_in, coef_out, dct_raw, raw_tile0);
-    else CSH_LAUNCH(k_xform_direct<false>, tile_grid(max_tiles, nwork), dim3(256), st, imgs, work, quant, coef_in, coef_out, dct_raw, raw_tile0);
+    if (dering) CSH_LAUNCH_PHASED(k_xform_direct<true>, CSH_NZF_PHASES, tile_grid(max_tiles, nwork), dim3(256), st, imgs, work, quant, coef_in, coef_out, dct_raw, raw_tile0, nzf);
+    else CSH_LAUNCH_PHASED(k_xform_direct<false>, CSH_NZF_PHASES, tile_grid(max_tiles, nwork), dim3(256), st, imgs, work, quant, coef_in, coef_out, dct_raw, raw_tile0, nzf);
 }
 void launch_idct_plane(hipStream_t st, const ImgDesc *imgs, const PlaneWork *work, int nwork, int max_tiles, const DevQuant *quant,
                        const int16_t *coef_in, uint8_t *planes) {
@@ -985,16 +1189,16 @@ void launch_resample_any(hipStream_t st, const ImgDesc *imgs, const PlaneWork *w
     if (nwork && max_quads) CSH_LAUNCH(k_resample_any, dim3((max_quads + 255) / 256, nwork), dim3(256), st, imgs, work, planes, oplanes);
 }
 void launch_plane_fdct(hipStream_t st, const ImgDesc *imgs, const PlaneWork *work, int nwork, int max_tiles, const DevQuant *quant,
-                       const uint8_t *oplanes, int16_t *coef_out, int16_t *dct_raw, uint32_t raw_tile0, bool dering) {
+                       const uint8_t *oplanes, int16_t *coef_out, int16_t *dct_raw, uint32_t raw_tile0, bool dering, const NzFuse &nzf) {
     if (!nwork) return;
-    if (dering) CSH_LAUNCH(k_plane_fdct<true>, tile_grid(max_tiles, nwork), dim3(256), st, imgs, work, quant, oplanes, coef_out, dct_raw, raw_tile0);
-    else CSH_LAUNCH(k_plane_fdct<false>, tile_grid(max_tiles, nwork), dim3(256), st, imgs, work, quant, oplanes, coef_out, dct_raw, raw_tile0);
+    if (dering) CSH_LAUNCH_PHASED(k_plane_fdct<true>, CSH_NZF_PHASES, tile_grid(max_tiles, nwork), dim3(256), st, imgs, work, quant, oplanes, coef_out, dct_raw, raw_tile0, nzf);
+    else CSH_LAUNCH_PHASED(k_plane_fdct<false>, CSH_NZF_PHASES, tile_grid(max_tiles, nwork), dim3(256), st, imgs, work, quant, oplanes, coef_out, dct_raw, raw_tile0, nzf);
 }
 void launch_resample_fdct_420(hipStream_t st, const ImgDesc *imgs, const PlaneWork *work, int nwork, int max_tiles, const DevQuant *quant,
-                              const uint8_t *planes, int16_t *coef_out, int16_t *dct_raw, uint32_t raw_tile0, bool dering) {
+                              const uint8_t *planes, int16_t *coef_out, int16_t *dct_raw, uint32_t raw_tile0, bool dering, const NzFuse &nzf) {
     if (!nwork) return;
-    if (dering) CSH_LAUNCH(k_resample_fdct_420<true>, tile_grid(max_tiles, nwork), dim3(256), st, imgs, work, quant, planes, coef_out, dct_raw, raw_tile0);
-    else CSH_LAUNCH(k_resample_fdct_420<false>, tile_grid(max_tiles, nwork), dim3(256), st, imgs, work, quant, planes, coef_out, dct_raw, raw_tile0);
+    if (dering) CSH_LAUNCH_PHASED(k_resample_fdct_420<true>, CSH_NZF_PHASES, tile_grid(max_tiles, nwork), dim3(256), st, imgs, work, quant, planes, coef_out, dct_raw, raw_tile0, nzf);
+    else CSH_LAUNCH_PHASED(k_resample_fdct_420<false>, CSH_NZF_PHASES, tile_grid(max_tiles, nwork), dim3(256), st, imgs, work, quant, planes, coef_out, dct_raw, raw_tile0, nzf);
 }
 void launch_requant(hipStream_t st, const ImgDesc *imgs, const PlaneWork *work, int nwork, int max_tiles, const DevQuant *quant, const int16_t *dct_raw,
                     uint32_t raw_tile0, int16_t *coef_out) {

@@ -86,8 +86,16 @@ void launch_dc_scatter(hipStream_t st, const ParScan *ps, int nps, uint32_t max_
 // direct: dequant -> jidctint -> range limit -> jfdctint -> quantise, one block per lane
 // dct_raw != nullptr: also keep the unquantised DCT (tile index relative to raw_tile0) for launch_requant
 // dering: mozjpeg's overshoot deringing on the level-shifted samples in front of every forward DCT (CSH_PROFILE=mozjpeg)
+// nzf: the level-0 coefficient lists (types.h NzList) of the work items that name an NzSet (PlaneWork::nzset) are built here, from the levels in
+// registers -- what k_nzlist (k_aclist.hip) would read the tiles again for.  nz_pool null: no list is built by this launch
+struct NzFuse {
+    const NzSet *nzsets; const NzList *nzlists;
+    uint32_t *nz_pool, *nz_cursor, *nz_chunk_off, *nz_chunk_cnt;   // EncCtx's; the cursors and the counts are zero when the launch starts
+    uint8_t *blk_cnt; uint16_t *blk_off;                           // EncCtx::nz_blk_cnt / nz_blk_off, or null
+    uint32_t *overflow;                                            // EncCtx::overflow
+};
 void launch_xform_direct(hipStream_t st, const ImgDesc *imgs, const PlaneWork *work, int nwork, int max_tiles, const DevQuant *quant,
-                         const int16_t *coef_in, int16_t *coef_out, int16_t *dct_raw, uint32_t raw_tile0, bool dering);
+                         const int16_t *coef_in, int16_t *coef_out, int16_t *dct_raw, uint32_t raw_tile0, bool dering, const NzFuse &nzf);
 void launch_requant(hipStream_t st, const ImgDesc *imgs, const PlaneWork *work, int nwork, int max_tiles, const DevQuant *quant, const int16_t *dct_raw,
                     uint32_t raw_tile0, int16_t *coef_out);
 // subsampled components: IDCT to a u8 plane (edges replicated), then resample + FDCT + quantise
@@ -95,9 +103,9 @@ void launch_idct_plane(hipStream_t st, const ImgDesc *imgs, const PlaneWork *wor
                        const int16_t *coef_in, uint8_t *planes);
 void launch_resample_plane(hipStream_t st, const ImgDesc *imgs, const PlaneWork *work, int nwork, uint32_t max_quads, const uint8_t *planes, uint8_t *oplanes);
 void launch_plane_fdct(hipStream_t st, const ImgDesc *imgs, const PlaneWork *work, int nwork, int max_tiles, const DevQuant *quant,
-                       const uint8_t *oplanes, int16_t *coef_out, int16_t *dct_raw, uint32_t raw_tile0, bool dering);
+                       const uint8_t *oplanes, int16_t *coef_out, int16_t *dct_raw, uint32_t raw_tile0, bool dering, const NzFuse &nzf);
 void launch_resample_fdct_420(hipStream_t st, const ImgDesc *imgs, const PlaneWork *work, int nwork, int max_tiles, const DevQuant *quant,
-                              const uint8_t *planes, int16_t *coef_out, int16_t *dct_raw, uint32_t raw_tile0, bool dering);
+                              const uint8_t *planes, int16_t *coef_out, int16_t *dct_raw, uint32_t raw_tile0, bool dering, const NzFuse &nzf);
 // every layout k_resample_plane does not take (PlaneWork.mode CSH_MODE_ANY): launched only when a batch has such items
 void launch_resample_any(hipStream_t st, const ImgDesc *imgs, const PlaneWork *work, int nwork, uint32_t max_quads, const uint8_t *planes, uint8_t *oplanes);
 void launch_fix_dummy(hipStream_t st, const ImgDesc *imgs, int nimg, int max_blocks, int16_t *coef_out);
@@ -162,6 +170,7 @@ struct EncCtx {  // device pointers + sizes every entropy kernel needs
     uint32_t nlist_slots;
     const uint32_t *tok_slots; // ... and those packed from tokens (k_pack); null: every slot of [slot0, slot0 + nslots)
     uint32_t ntok_slots;
+    uint32_t nz_build, nz_filter; // the run's NzChunks: some asks for level 0 from the tiles (k_nzlist) / for a filtered level (k_nzfilter); a kernel nobody asks for is not launched
 };
 void launch_tokens(hipStream_t st, const EncCtx &c);
 void launch_ac_runs(hipStream_t st, const EncCtx &c);

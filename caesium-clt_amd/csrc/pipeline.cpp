@@ -267,6 +267,7 @@ static int batch_run(csh_batch *b, csh_timing *t, bool requant_only) {
         for (uint32_t v : ns) { if (v == 4) { t->n_prog_decoded++; continue; } if (v) t->n_seq_decoded++; if (v == 2 || v == 3) t->n_par_fallback++; if (v == 3) t->n_par_short++; }
         t->n_images = uint32_t(b->nimg);
         t->n_search_extra = b->enc.search ? b->enc.n_gated_runs : 0u;
+        t->n_fused_lists = b->enc.last_run_fused;
         for (const Item &it : b->items) if (it.image < 0) t->n_failed++;
         for (int i = 0; i < b->nimg; i++) { t->out_bytes += b->out.h_img_size[i]; t->pixels += uint64_t(b->imgs[i].width) * b->imgs[i].height; }
         t->in_bytes = b->dec.bits_pool.size();

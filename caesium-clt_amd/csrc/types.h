@@ -169,6 +169,7 @@ struct PlaneWork {
     int mode;
     UpDesc up;     // the decoded plane (resize path: the full-resolution plane of the resized image, CSH_UP_COPY)
     int dn;        // CSH_DN_*: the encoder's downsampling
+    uint32_t nzset; // the component's NzSet when the forward-DCT kernel builds its level-0 list (k_pixel.hip nzf_*: real_bw == bw, so a workgroup's 256 blocks are a list chunk); 0xFFFFFFFF: not here
 };
 
 // resize path work item (k_resize.hip): one image

@@ -133,6 +133,8 @@ typedef struct {
     uint32_t n_prog_decoded;      /* progressive inputs decoded by the wave-per-chain kernel (not counted in n_seq_decoded) */
     uint32_t n_refine_chains;     /* chains of AC refinement scans (progressive inputs) taken by the parse + apply kernels (k_decode_refine.hip) */
     uint32_t n_search_extra;      /* conditional stages of the scan search this run needed (0..3: luma at Al 3, the fourth and the fifth frequency split) */
+    uint32_t n_fused_lists;       /* components whose level-0 coefficient list the forward-DCT kernels built in this run (0 with CSH_NZ_FUSED=0, in a re-quantisation run, and
+                                     for components whose width is not a multiple of the MCU width: k_nzlist builds those from the tiles) */
 } csh_timing;
 
 int csh_device_count(void);
