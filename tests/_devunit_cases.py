@@ -1,0 +1,771 @@
+"""The battery of the device-unit tests (tests/devunit/README.md): inputs with fixed seeds, expected values, the loader of the unit library, and one
+checking function per unit.  tests/test_device_units_emul.py drives the emulation build of the library through it, tests/test_device_units_gpu.py the
+gfx950 build -- the same bytes in, the same values expected, so the two branches of a CSH_EMUL conditional answer to one statement.
+
+Where the expected values come from: numpy / Python integer arithmetic written here from the operation's definition, and the oracle's plain routines
+cso_fdct_islow, cso_idct_islow and cso_dering_block.  Never from either build of the library, nor from another function of the file under test.
+Every comparison is exact."""
+import ctypes as C
+import functools
+import os
+import subprocess
+
+import numpy as np
+
+from _util import PKG_DIR, ROOT
+
+DEVICE_ONLY = -100   # what an entry answers that has no emulation form (tests/devunit/du_entropy.cpp)
+ZZ = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+               35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63])   # zig-zag -> natural
+SEAM_LANES = [0, 15, 16, 31, 32, 63]   # either side of the rows of 16 and the banks of 32 the DPP ladders are built from
+M32 = (1 << 32) - 1
+
+
+# ---------------------------------------------------------------------------------------------------- the library
+class Lib:
+    def __init__(self, path):
+        self.path = path
+        self.dll = C.CDLL(path)
+        self.dll.csdu_sizeof_devquant.restype = C.c_size_t
+        self.emul = bool(self.dll.csdu_is_emul())
+
+    def call(self, fn, *args):
+        """an entry with numpy arrays (passed by address), ints and size_t (given as ("z", n)); -> its return code"""
+        conv = []
+        for a in args:
+            if isinstance(a, np.ndarray):
+                assert a.flags["C_CONTIGUOUS"]
+                conv.append(C.c_void_p(a.ctypes.data))
+            elif isinstance(a, tuple):
+                conv.append(C.c_size_t(a[1]))
+            else:
+                conv.append(C.c_int(int(a)))
+        f = getattr(self.dll, fn)
+        f.restype = C.c_int
+        return f(*conv)
+
+    def run(self, fn, *args):
+        rc = self.call(fn, *args)
+        assert rc == 0, f"{fn}: the entry returned {rc} (a HIP error code; -1: arguments refused)"
+
+    def quant(self, natural):
+        """DevQuant (as bytes in a numpy array) of a table in natural order"""
+        q = np.zeros(self.dll.csdu_sizeof_devquant(), np.uint8)
+        self.dll.csdu_make_quant.restype = None
+        self.dll.csdu_make_quant(C.c_void_p(np.ascontiguousarray(natural, np.uint16).ctypes.data), C.c_void_p(q.ctypes.data))
+        return q
+
+
+def _sources():
+    csrc, du = os.path.join(PKG_DIR, "csrc"), os.path.join(ROOT, "tests", "devunit")
+    return [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".cpp", ".h", ".hpp"))] + [os.path.join(du, f) for f in os.listdir(du) if f.endswith((".cpp", ".h"))]
+
+
+@functools.lru_cache(None)
+def emul_lib():
+    """the g++ -DCSH_EMUL build of the units, rebuilt through make when a source is newer (as _util.emul_api does for the library)"""
+    so = os.path.join(ROOT, "tests", "emul", "libcsh_devunit_emul.so")
+    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in _sources()):
+        subprocess.check_call(["make", "-s", "-C", os.path.join(PKG_DIR, "csrc"), "../../tests/emul/libcsh_devunit_emul.so"])
+    lib = Lib(so)
+    assert lib.emul
+    return lib
+
+
+@functools.lru_cache(None)
+def device_lib():
+    """the gfx950 build (made by `make` in caesium-clt_amd/csrc, so by build()).  A missing library or no device is an error of the caller's, never a skip."""
+    so = os.path.join(ROOT, "tests", "devunit", "libcsh_devunit.so")
+    assert os.path.exists(so), f"{so} is missing: run `make -C caesium-clt_amd/csrc` (build() does)"
+    lib = Lib(so)
+    assert not lib.emul
+    n = lib.dll.csdu_device_count()
+    assert n >= 1, f"no HIP device visible (csdu_device_count() = {n}); the device units have no CPU form"
+    return lib
+
+
+def same(what, got, want):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: the test compares {got.dtype}{got.shape} with {want.dtype}{want.shape}"
+    if np.array_equal(got, want):
+        return
+    bad = np.flatnonzero(got.ravel() != want.ravel())
+    at = np.unravel_index(bad[0], got.shape)
+    raise AssertionError(f"{what}: {bad.size} of {got.size} values differ; the first at {tuple(int(i) for i in at)}: got {got[at]!r}, expected {want[at]!r}")
+
+
+def _oracle():
+    from oracle import oracle as O
+    L = O.lib()
+    L.cso_dering_block.argtypes = [C.c_void_p, C.c_int]
+    L.cso_dering_block.restype = None
+    return L
+
+
+class Lcg:
+    """the generator of tests/xform_block_check.cpp (state * 1664525 + 1013904223, the top 24 bits), as one array: its blocks are that check's blocks"""
+    def __init__(self, n, seed=12345):
+        a = np.full(n, 1664525, np.uint32)
+        a[0] = 1
+        an = np.cumprod(a, dtype=np.uint32)                                   # a^i mod 2^32
+        geo = np.concatenate([[0], np.cumsum(an[:-1], dtype=np.uint32)]).astype(np.uint32)   # 1 + a + .. + a^(i-1)
+        st0 = an * np.uint32(seed) + geo * np.uint32(1013904223)              # the state BEFORE draw i
+        self.v = ((st0 * np.uint32(1664525) + np.uint32(1013904223)) >> np.uint32(8)).astype(np.int64)
+        self.at = 0
+
+    def take(self, n):
+        r = self.v[self.at:self.at + n]
+        assert len(r) == n
+        self.at += n
+        return r
+
+
+# ---------------------------------------------------------------------------------------------------- block arithmetic: references
+def fdct_islow(s):
+    """jfdctint.c (the accurate integer forward DCT, CONST_BITS 13, PASS1_BITS 2) on level-shifted samples [N, 64] natural order, in int64: rows, then columns"""
+    def descale(x, n):
+        return (x + (1 << (n - 1))) >> n
+
+    def pass1d(d, first):
+        d0, d1, d2, d3, d4, d5, d6, d7 = (d[..., i] for i in range(8))
+        tmp0, tmp7, tmp1, tmp6, tmp2, tmp5, tmp3, tmp4 = d0 + d7, d0 - d7, d1 + d6, d1 - d6, d2 + d5, d2 - d5, d3 + d4, d3 - d4
+        tmp10, tmp13, tmp11, tmp12 = tmp0 + tmp3, tmp0 - tmp3, tmp1 + tmp2, tmp1 - tmp2
+        sh = 11 if first else 15
+        o = [None] * 8
+        o[0] = (tmp10 + tmp11) << 2 if first else descale(tmp10 + tmp11, 2)
+        o[4] = (tmp10 - tmp11) << 2 if first else descale(tmp10 - tmp11, 2)
+        z1 = (tmp12 + tmp13) * 4433
+        o[2], o[6] = descale(z1 + tmp13 * 6270, sh), descale(z1 + tmp12 * -15137, sh)
+        z1, z2, z3, z4 = tmp4 + tmp7, tmp5 + tmp6, tmp4 + tmp6, tmp5 + tmp7
+        z5 = (z3 + z4) * 9633
+        tmp4, tmp5, tmp6, tmp7 = tmp4 * 2446, tmp5 * 16819, tmp6 * 25172, tmp7 * 12299
+        z1, z2, z3, z4 = z1 * -7373, z2 * -20995, z3 * -16069 + z5, z4 * -3196 + z5
+        o[7], o[5], o[3], o[1] = descale(tmp4 + z1 + z3, sh), descale(tmp5 + z2 + z4, sh), descale(tmp6 + z2 + z3, sh), descale(tmp7 + z1 + z4, sh)
+        return np.stack(o, axis=-1)
+
+    x = np.asarray(s, np.int64).reshape(-1, 8, 8)
+    x = pass1d(x, True)                                  # along a row
+    x = pass1d(x.transpose(0, 2, 1), False).transpose(0, 2, 1)   # along a column
+    return x.reshape(-1, 64)
+
+
+def quantise(w_zz, q_zz):
+    """libjpeg's scalar rule on the DCT scaled by 8: sign(w) ((|w| + d / 2) / d), d = 8 q"""
+    d = np.asarray(q_zz, np.int64)[None, :] * 8
+    a = np.abs(w_zz)
+    lv = (a + (d >> 1)) // d
+    return np.where(w_zz < 0, -lv, lv)
+
+
+def dering(samples, dc_quant):
+    """cso_dering_block on every block of level-shifted samples [N, 64]"""
+    L = _oracle()
+    out = np.ascontiguousarray(samples, np.int32).copy()
+    base = out.ctypes.data
+    for i in range(out.shape[0]):
+        L.cso_dering_block(base + 256 * i, int(dc_quant))
+    return out
+
+
+BASE_TABLE = np.array([16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+                       18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99])
+
+
+def check_tables():
+    """the three tables of tests/xform_block_check.cpp, natural order: all ones, its q-80 table, base x 50 (16-bit values)"""
+    return [np.ones(64, np.int64), np.maximum((BASE_TABLE * 40 + 50) // 100, 1), BASE_TABLE * 50]
+
+
+@functools.lru_cache(None)
+def fdct_battery():
+    """-> [(table (natural), samples [N, 64] level-shifted natural order)] for the three tables: the inputs of tests/xform_block_check.cpp"""
+    per = [[], [], []]
+    y, x = np.mgrid[0:8, 0:8]
+    for hi in (127, 158):
+        for u in range(8):
+            for v in range(8):
+                for neg in (0, 1):
+                    c = np.cos((2 * x + 1) * u * np.pi / 16) * np.cos((2 * y + 1) * v * np.pi / 16)
+                    s = np.where((c >= 0) != (neg != 0), hi, -128).reshape(64)
+                    for t in range(3):
+                        per[t].append(s)
+    for v in (-128, -1, 0, 1, 127, 158):
+        per[1].append(np.full(64, v))
+    g = Lcg(20000 * 64 * 2)
+    row = (np.arange(64) // 8) * 9 - 30
+    for t in range(20000):
+        kind = t % 3
+        if kind == 0:
+            s = g.take(64) % 287 - 128
+        elif kind == 1:
+            r = g.take(128).reshape(64, 2)
+            s = np.where(r[:, 0] & 7, r[:, 1] % 17 - 8, np.where(r[:, 1] & 1, 158, -128))
+        else:
+            s = g.take(64) % 33 - 16 + row
+        per[t % 3].append(s)
+    fdct_battery.lcg_end = g.at
+    return [(tb, np.array(p, np.int64)) for tb, p in zip(check_tables(), per)]
+
+
+@functools.lru_cache(None)
+def fdct_expected(dering_on):
+    """-> per table (retained DCT int16 [N, 64] zig-zag, levels int16 [N, 64] zig-zag).  The numpy statement of jfdctint is itself held against
+    cso_fdct_islow on every block the oracle's routine takes (samples within 8 bits)."""
+    L = _oracle()
+    out = []
+    for tb, s in fdct_battery():
+        if dering_on:
+            s = dering(s, tb[0]).astype(np.int64)
+        w = fdct_islow(s)
+        in8 = np.flatnonzero((s <= 127).all(axis=1) & (s >= -128).all(axis=1))
+        s8 = np.ascontiguousarray(s[in8] + 128, np.uint8)
+        o = np.zeros((len(in8), 64), np.int32)
+        for i in range(len(in8)):
+            L.cso_fdct_islow(s8.ctypes.data + 64 * i, o.ctypes.data + 256 * i)
+        same("the test's own jfdctint statement against cso_fdct_islow", w[in8].astype(np.int32), o)
+        wz = w[:, ZZ]
+        assert np.abs(wz).max() < 32768
+        out.append((wz.astype(np.int16), quantise(wz, tb[ZZ]).astype(np.int16)))
+    return out
+
+
+FDCT_FORMS = ["fdct_quant_store<false, true>", "fdct_quant_store<false, false>", "fdct_quant_store_pk<false, false>", "fdct_quant_store_pk<false, true>",
+              "fdct_quant_store_pk<true, false>", "fdct_quant_store_pk<true, true>"]
+
+
+def run_fdct(lib, variant, nthreads, table, samples):
+    n = samples.shape[0]
+    raw, lev = np.zeros((n, 64), np.int16), np.zeros((n, 64), np.int16)
+    lib.run("csdu_fdct", variant, nthreads, n, np.ascontiguousarray(samples, np.int16), lib.quant(table), raw, lev)
+    return raw, lev
+
+
+def unit_fdct(lib, variant, nthreads):
+    name = f"{FDCT_FORMS[variant]} [{nthreads} threads]"
+    for t, ((tb, s), (wraw, wlev)) in enumerate(zip(fdct_battery(), fdct_expected(variant >= 4))):
+        raw, lev = run_fdct(lib, variant, nthreads, tb, s)
+        same(f"{name}, table {t}: the retained DCT (dering_block_pk + fdct1d_pk)" if variant >= 4 else f"{name}, table {t}: the retained DCT (fdct1d_pk)", raw, wraw)
+        same(f"{name}, table {t}: the quantised levels (quant_one)", lev, wlev)
+
+
+# ---- deringing
+@functools.lru_cache(None)
+def dering_blocks():
+    """-> (blocks with samples at the top of the range [N, 64], blocks without [M, 64]); level-shifted, natural order"""
+    rng = np.random.default_rng(20240611)
+    hot = []
+    for flavour in range(2):
+        def ground():
+            return np.full(64, 90) if flavour == 0 else rng.integers(-128, 127, 64)   # (126 at the most: not at the top)
+        hot.append(np.full(64, 127))                                   # all 64: skipped
+        for p in range(64):                                            # one sample, at every position
+            b = ground(); b[p] = 127; hot.append(b)
+        for length in range(1, 64):                                    # a run of every length at the start, the middle and the end of the walk (zig-zag) order
+            for start in (0, (64 - length) // 2, 64 - length):
+                b = ground(); b[ZZ[start:start + length]] = 127; hot.append(b)
+    cold = [np.full(64, 126), np.full(64, -128), np.zeros(64, np.int64)] + [rng.integers(-128, 127, 64) for _ in range(125)]
+    return np.array(hot, np.int64), np.array(cold, np.int64)
+
+
+@functools.lru_cache(None)
+def dering_layout():
+    """the blocks lane by lane.  Waves 0..4: no lane holds a block for deringing (the ballot exit), only lane 0, only lane 63, alternate lanes, (from wave 4 on)
+    all lanes.  -> samples [N, 64], N a multiple of 256"""
+    hot, cold = dering_blocks()
+    w0 = cold[:64]
+    w1 = np.concatenate([hot[70:71], cold[64:127]])
+    w2 = np.concatenate([cold[1:64], hot[200:201]])
+    w3 = np.stack([hot[300 + i // 2] if i % 2 == 0 else cold[i] for i in range(64)])
+    allb = np.concatenate([w0, w1, w2, w3, hot])
+    pad = (-len(allb)) % 256
+    return np.concatenate([allb, cold[:pad]]) if pad else allb
+
+
+@functools.lru_cache(None)
+def dering_tables():
+    """the luma tables of the project's profile (mozjpeg's table 3) at qualities 1, 50, 80, 100: DC steps 2 x which is above and below the overshoot's cap of 31,
+    8-bit and 16-bit entries"""
+    L = _oracle()
+    out = []
+    for quality in (1, 50, 80, 100):
+        t = np.zeros((2, 64), np.uint16)
+        L.cso_quality_tables(quality, 3, 0, t.ctypes.data)
+        out.append((quality, t[0].astype(np.int64)))
+    assert max(int(t.max()) for _, t in out) > 255 and out[-1][1][0] == 1
+    return out
+
+
+@functools.lru_cache(None)
+def dering_expected():
+    s = dering_layout()
+    out = []
+    for quality, tb in dering_tables():
+        d = dering(s, tb[0]).astype(np.int64)
+        hot, cold = dering_blocks()
+        assert np.array_equal(d[:64], s[:64]) and (d != s).any()   # blocks without a sample at the top come back untouched
+        wz = fdct_islow(d)[:, ZZ]
+        out.append((wz.astype(np.int16), quantise(wz, tb[ZZ]).astype(np.int16)))
+    return out
+
+
+def unit_dering(lib, centred, nthreads):
+    variant = 5 if centred else 4
+    name = f"dering_block_pk<{'true' if centred else 'false'}> through {FDCT_FORMS[variant]} [{nthreads} threads]"
+    s = dering_layout()
+    for (quality, tb), (wraw, wlev) in zip(dering_tables(), dering_expected()):
+        raw, lev = run_fdct(lib, variant, nthreads, tb, s)
+        same(f"{name}, DC step {tb[0]} (quality {quality}): the DCT of the deringed block", raw, wraw)
+        same(f"{name}, DC step {tb[0]} (quality {quality}): the levels", lev, wlev)
+
+
+# ---- inverse transform
+@functools.lru_cache(None)
+def idct_battery():
+    """-> [(table (natural), coefficients [N, 64] zig-zag int16)] for tables 0 and 1: the inputs of tests/xform_block_check.cpp's inverse check"""
+    tabs = check_tables()
+    per = [[], []]
+    for dc in range(-1024, 1025):
+        c = np.zeros(64, np.int64); c[0] = dc; per[0].append(c)
+    for k in range(64):
+        for v in (-1023, -512, -1, 1, 512, 1023):
+            c = np.zeros(64, np.int64); c[k] = v; per[0].append(c)
+            c = c.copy(); c[0] = 300; per[0].append(c)
+    fdct_battery()
+    g = Lcg(fdct_battery.lcg_end + 20000 * 42)
+    g.at = fdct_battery.lcg_end   # the check draws its sparse blocks from the same stream, behind the forward check's
+    trunc = lambda a, b: int(abs(a) // b) * (1 if a >= 0 else -1)   # C's division
+    for t in range(20000):
+        qz = tabs[t % 2][ZZ]
+        c = np.zeros(64, np.int64)
+        c[0] = trunc(int(g.take(1)[0]) % 2049 - 1024, int(qz[0]))
+        n = int(g.take(1)[0]) % 20
+        r = g.take(2 * n)
+        for j in range(n):
+            k = 1 + int(r[2 * j]) % 63
+            c[k] = trunc(int(r[2 * j + 1]) % 401 - 200, int(qz[k]))
+        per[t % 2].append(c)
+    return [(tabs[i], np.array(per[i], np.int16)) for i in range(2)]
+
+
+@functools.lru_cache(None)
+def idct_expected():
+    """cso_idct_islow's samples (0..255), natural order, per table"""
+    L = _oracle()
+    out = []
+    for tb, cz in idct_battery():
+        nat = np.zeros_like(cz)
+        nat[:, ZZ] = cz
+        qn = np.ascontiguousarray(tb, np.uint16)
+        px = np.zeros((len(cz), 64), np.uint8)
+        for i in range(len(cz)):
+            L.cso_idct_islow(nat.ctypes.data + 128 * i, qn.ctypes.data, px.ctypes.data + 64 * i)
+        out.append(px.astype(np.int16))
+    return out
+
+
+def unit_idct(lib, centred, nthreads):
+    name = f"load_idct<{'true' if centred else 'false'}> [{nthreads} threads]"
+    for t, ((tb, cz), want) in enumerate(zip(idct_battery(), idct_expected())):
+        got = np.zeros((len(cz), 64), np.int16)
+        lib.run("csdu_idct", int(centred), nthreads, len(cz), cz, lib.quant(tb), got)
+        same(f"{name}, table {t}: the samples against cso_idct_islow", got + np.int16(128 if centred else 0), want)
+
+
+# ---------------------------------------------------------------------------------------------------- packed primitives
+@functools.lru_cache(None)
+def pk_words():
+    """-> a, b (uint32), acc (int32): every pairing of the words made of halves 0, 1, 0x7FFF, 0x8000, 0xFFFF, and 10^5 random words"""
+    h = [0, 1, 0x7FFF, 0x8000, 0xFFFF]
+    w = np.array([lo | (hi << 16) for lo in h for hi in h], np.uint32)
+    a, b = np.repeat(w, len(w)), np.tile(w, len(w))
+    accs = np.array([0, 1, -1, 0x7FFFFFFF, -0x80000000, 1 << 10, 1 << 14, 2 - 32768], np.int64)
+    rng = np.random.default_rng(7)
+    ra, rb = rng.integers(0, 1 << 32, 100000, dtype=np.uint64).astype(np.uint32), rng.integers(0, 1 << 32, 100000, dtype=np.uint64).astype(np.uint32)
+    acc = np.concatenate([accs[np.arange(len(a)) % len(accs)], rng.integers(-1 << 31, 1 << 31, 100000)]).astype(np.int32)
+    return np.concatenate([a, ra]), np.concatenate([b, rb]), acc
+
+
+def _halves(w):
+    w = w.astype(np.int64)
+    return ((w & 0xFFFF) ^ 0x8000) - 0x8000, ((w >> 16) ^ 0x8000) - 0x8000   # the two halves as signed 16-bit values
+
+
+def _join(lo, hi):
+    return ((lo & 0xFFFF) | ((hi & 0xFFFF) << 16)).astype(np.uint32)
+
+
+PK_OPS = ["pk_add", "pk_sub", "pk_max", "dot2", "pack_halves", "pack_hi_halves", "bytes_to_halves<0, 1>", "bytes_to_halves<2, 3>", "bytes_to_halves<3, 2>", "bytes_to_halves<1, 0>", "nzf_ones"]
+
+
+def pk_expected(op):
+    a, b, acc = pk_words()
+    (al, ah), (bl, bh), A, B = _halves(a), _halves(b), a.astype(np.int64), b.astype(np.int64)
+    if op == 0: return _join(al + bl, ah + bh)
+    if op == 1: return _join(al - bl, ah - bh)
+    if op == 2: return _join(np.maximum(al, bl), np.maximum(ah, bh))
+    if op == 3: return ((acc.astype(np.int64) + al * bl + ah * bh) & M32).astype(np.uint32)
+    if op == 4: return _join(A, B)
+    if op == 5: return _join(A >> 16, B >> 16)
+    if op == 10: return _join((al != 0).astype(np.int64), (ah != 0).astype(np.int64))   # 1 in every half that is not zero
+    i0, i1 = [(0, 1), (2, 3), (3, 2), (1, 0)][op - 6]
+    return _join((A >> (8 * i0)) & 255, (A >> (8 * i1)) & 255)
+
+
+def unit_pk(lib, op):
+    a, b, acc = pk_words()
+    out = np.zeros(len(a), np.uint32)
+    lib.run("csdu_pk", op, len(a), a, b, acc, out)
+    same(f"{PK_OPS[op]} (k_pixel.hip)", out, pk_expected(op))
+
+
+def unit_pk_abs16(lib):
+    a, _, _ = pk_words()
+    out = np.zeros(len(a), np.uint32)
+    lib.run("csdu_abs16", len(a), a, out)
+    lo, hi = _halves(a)
+    same("pk_abs16 (k_entropy.hip)", out, _join(np.abs(lo), np.abs(hi)))   # |-32768| stays 0x8000, as 16-bit arithmetic has it
+
+
+# ---------------------------------------------------------------------------------------------------- wave helpers (png_wave.h, wave.h)
+@functools.lru_cache(None)
+def wave_words():
+    """[nwaves, 64] uint32, nwaves a multiple of 8 (two workgroups of four waves): neighbouring waves hold different data"""
+    rng = np.random.default_rng(11)
+    rows = [np.zeros(64), np.ones(64), np.arange(64), np.full(64, M32)]
+    for k in SEAM_LANES:
+        r = np.zeros(64); r[k] = 0x9E3779B1; rows.append(r)
+    rows += [rng.integers(0, 1 << 32, 64) for _ in range(10)] + [rng.integers(0, 2, 64) * rng.integers(0, 1 << 32, 64) for _ in range(4)]
+    order = rng.permutation(len(rows))
+    x = np.array(rows, np.uint64)[order].astype(np.uint32)
+    assert len(x) % 8 == 0
+    return x
+
+
+WAVE32_OPS = ["lscan", "lsum32", "lprev", "llast", "lget", "lset", "lballot", "uni"]
+
+
+def unit_wave32(lib, op, wpb):
+    x = wave_words()
+    nw = len(x)
+    rng = np.random.default_rng(13 + op)
+    arg = np.zeros((nw, 2), np.uint32)
+    lanes = np.array([(SEAM_LANES + [1, 47])[i % 8] for i in range(nw)])
+    arg[:, 0] = rng.integers(0, 1 << 32, nw) if op in (2, 7) else lanes
+    arg[:, 1] = rng.integers(0, 1 << 32, nw)
+    out, out2 = np.zeros_like(x), np.zeros_like(x)
+    lib.run("csdu_wave32", op, nw, wpb, x, arg, out, out2)
+    X = x.astype(np.uint64)
+    incl = np.cumsum(X, axis=1) & M32
+    every = lambda v: np.repeat(np.asarray(v, np.uint64).astype(np.uint32)[:, None], 64, axis=1)
+    name = f"{WAVE32_OPS[op]} [{wpb * 64} threads]"
+    if op == 0:
+        same(f"{name}: the exclusive prefix sums", out, ((incl - X) & M32).astype(np.uint32))
+        same(f"{name}: the total, in every lane", out2, every(incl[:, 63]))
+    elif op == 1:
+        same(f"{name}: the sum mod 2^32, in every lane", out, every(X.sum(axis=1) & M32))
+    elif op == 2:
+        want = np.roll(x, 1, axis=1); want[:, 0] = arg[:, 0]
+        same(f"{name}: lane l takes lane l - 1, lane 0 the carry", out, want)
+    elif op == 3:
+        same(f"{name}: lane 63's value, in every lane", out, every(x[:, 63]))
+    elif op == 4:
+        same(f"{name}: the chosen lane's value, in every lane", out, every(x[np.arange(nw), lanes]))
+    elif op == 5:
+        want = x.copy(); want[np.arange(nw), lanes] = arg[:, 1]
+        same(f"{name}: the value in the chosen lane, the others as they were", out, want)
+    elif op == 6:
+        m = ((x != 0).astype(np.uint64) << np.arange(64, dtype=np.uint64)[None, :]).sum(axis=1, dtype=np.uint64)
+        same(f"{name}: the low word", out, every(m & np.uint64(M32)))
+        same(f"{name}: the high word", out2, every(m >> np.uint64(32)))
+    else:
+        same(f"{name}: the wave-uniform value, in every lane", out, every(arg[:, 0]))
+
+
+@functools.lru_cache(None)
+def wave_longs():
+    """[nwaves, 64] uint64: random; values that differ only above / only below bit 32 (the device moves the halves separately); equal minima; extremes"""
+    rng = np.random.default_rng(17)
+    r64 = lambda: rng.integers(0, 1 << 32, 64).astype(np.uint64) << np.uint64(32) | rng.integers(0, 1 << 32, 64).astype(np.uint64)
+    rows = [r64() for _ in range(6)]
+    rows += [(rng.integers(0, 1 << 32, 64).astype(np.uint64) << np.uint64(32)) | np.uint64(0x89ABCDEF) for _ in range(3)]        # differ above bit 32 only
+    rows += [(np.uint64(0x01234567) << np.uint64(32)) | rng.integers(0, 1 << 32, 64).astype(np.uint64) for _ in range(3)]        # below bit 32 only
+    hi_lo = np.where(np.arange(64) % 2 == 0, np.uint64(0x00000001FFFFFFFF), np.uint64(0x0000000200000000))                      # a smaller high half with a larger low half
+    rows += [hi_lo, hi_lo[::-1].copy(), np.full(64, (1 << 64) - 1, np.uint64), np.zeros(64, np.uint64)]
+    for k in SEAM_LANES:                                                                                                        # the minimum in one lane; then twice
+        r = np.full(64, 0xFFFFFFFF00000000, np.uint64); r[k] = 0xFFFFFFFE00000005; rows.append(r)
+    r = r64() | np.uint64(1 << 63); r[5] = r[40] = 77; rows.append(r)
+    r = r64() | np.uint64(1 << 63); rows.append(r)
+    x = np.array(rows, np.uint64)[rng.permutation(len(rows))]
+    assert len(x) % 8 == 0, len(x)
+    return x
+
+
+def unit_wave64(lib, op, wpb):
+    x = wave_longs()
+    out = np.zeros_like(x)
+    lib.run("csdu_wave64", op, len(x), wpb, x, out)
+    want = np.array([sum(int(v) for v in row) & ((1 << 64) - 1) for row in x], np.uint64) if op == 0 else x.min(axis=1)
+    same(f"{['lsum', 'lmin64'][op]} [{wpb * 64} threads]: in every lane", out, np.repeat(want[:, None], 64, axis=1))
+
+
+# ---------------------------------------------------------------------------------------------------- k_entropy.hip
+ESCAN_OPS = ["wave_scan_dpp with +", "wave_scan_dpp with |", "wave_incl_scan", "wave_last", "wave_last of wave_incl_sum"]
+
+
+def unit_escan(lib, op, nthreads):
+    """ops 0..2: whole waves.  3, 4: also workgroups of 65 and 96 threads, whose last wave has 1 and 32 active lanes -- what wave_last's ballot is there for"""
+    rng = np.random.default_rng(23 + op)
+    nblocks = 3
+    n = nblocks * nthreads
+    x = rng.integers(0, 1 << 32, n).astype(np.uint32)
+    if nthreads % 64 == 0:
+        x[:64] = M32             # the sum wraps
+        x[64:128] = 0
+        x[64 + 16] = 5           # one lane, at a row seam
+    if op == 2:
+        x &= np.uint32(0xFFFF)   # (the counts k_tokens scans; the variant with other values in the high halves: unit_incl_scan_high_halves)
+    out = np.zeros(n, np.uint32)
+    rc = lib.call("csdu_escan", op, nblocks, nthreads, x, out)
+    name = f"{ESCAN_OPS[op]} [{nthreads} threads]"
+    if lib.emul and op != 2:
+        assert rc == DEVICE_ONLY, f"{name}: exists in the product build only, and the emulation build's entry should say so (returned {rc})"
+        return
+    assert rc == 0, f"{name}: the entry returned {rc}"
+    want = np.zeros(n, np.uint32)
+    for b in range(nblocks):
+        for w0 in range(0, nthreads, 64):
+            lo, hi = b * nthreads + w0, b * nthreads + min(w0 + 64, nthreads)   # the wave's active lanes
+            v = x[lo:hi].astype(np.uint64)
+            if op in (0, 2): want[lo:hi] = np.cumsum(v) & M32
+            elif op == 1: want[lo:hi] = np.bitwise_or.accumulate(v)
+            elif op == 3: want[lo:hi] = v[-1]
+            else: want[lo:hi] = int(v.sum()) & M32
+    same(name, out, want)
+
+
+def unit_incl_scan_high_halves(lib, nthreads):
+    """wave_incl_scan's inputs as k_tokens' emulation sees them: the scan's own results already packed into the high halves of the words of the lanes that ran.
+    The device form scans whole words (its high halves are still zero then); what both forms promise of such words is the low half of the result."""
+    rng = np.random.default_rng(29)
+    n = 2 * nthreads
+    cnt = rng.integers(0, 600, n).astype(np.uint32)   # a wave's total stays below 2^16
+    x = cnt | (rng.integers(0, 1 << 16, n).astype(np.uint32) << np.uint32(16))
+    out = np.zeros(n, np.uint32)
+    lib.run("csdu_escan", 2, 2, nthreads, x, out)
+    want = np.cumsum(cnt.reshape(-1, 64).astype(np.uint64), axis=1).reshape(-1).astype(np.uint32)
+    same(f"wave_incl_scan [{nthreads} threads], junk in the high halves: the low half of the scan", out & np.uint32(0xFFFF), want)
+    if lib.emul:
+        same(f"wave_incl_scan [{nthreads} threads], junk in the high halves: the emulation masks them", out, want)
+
+
+def unit_or64(lib, nthreads):
+    """the device: the OR of the wave's values.  The emulation, whose lanes cannot see each other, promises a superset (all ones) -- callers only skip work on 0."""
+    rng = np.random.default_rng(31)
+    n = 4 * nthreads
+    x = (np.uint64(1) << rng.integers(0, 64, n).astype(np.uint64)) * rng.integers(0, 2, n).astype(np.uint64)
+    x[:64] = 0
+    x[64:128] = 0
+    x[64 + 31] = np.uint64(1) << np.uint64(32)
+    x[128 + 32] |= np.uint64(0x8000000000000001)
+    out = np.zeros(n, np.uint64)
+    lib.run("csdu_or64", 4, nthreads, x, out)
+    want = np.repeat(np.bitwise_or.reduce(x.reshape(-1, 64), axis=1), 64)
+    if lib.emul:
+        same(f"wave_or64 [{nthreads} threads]: the emulation's answer holds every bit of the OR", out & want, want)
+    else:
+        same(f"wave_or64 [{nthreads} threads]: the OR over the wave, in every lane", out, want)
+
+
+# ---------------------------------------------------------------------------------------------------- k_vp8enc.hip
+@functools.lru_cache(None)
+def row_words():
+    rng = np.random.default_rng(37)
+    rows = [rng.integers(-(1 << 20), 1 << 20, 64) for _ in range(13)] + [np.full(64, -1), np.arange(64) - 32, np.zeros(64)]
+    for k in (0, 7, 8, 15, 16, 63):
+        r = np.zeros(64); r[k] = -12345; rows.append(r)
+    rows += [rng.integers(-3, 4, 64), rng.integers(-(1 << 20), 1 << 20, 64)]
+    x = np.array(rows, np.int64)[rng.permutation(len(rows))].astype(np.int32)
+    assert len(x) % 8 == 0, len(x)
+    return x
+
+
+def unit_row32(lib, op, wpb):
+    x = row_words()
+    out = np.zeros_like(x)
+    lib.run("csdu_row32", op, len(x), wpb, x, out)
+    lane = np.arange(64)
+    if op == 0: want = np.repeat(x.reshape(-1, 4, 16).sum(axis=2, dtype=np.int64), 16, axis=1)
+    elif op == 1: want = np.repeat(x.reshape(-1, 8, 8).sum(axis=2, dtype=np.int64), 8, axis=1)
+    elif op == 2: want = x[:, lane & 48]
+    else: want = x[:, (lane & 48) + 8]
+    same(f"{['rowsum', 'halfsum', '__shfl of lane l & 48', '__shfl of lane (l & 48) + 8'][op]} (k_vp8enc.hip) [{wpb * 64} threads]", out, want.reshape(x.shape).astype(np.int32))
+
+
+def unit_row64(lib, op, wpb):
+    x = wave_longs().copy()
+    x[0, :] = np.where(np.arange(64) % 3 == 0, np.uint64(0x0000000500000009), np.uint64(0x0000000500000009) + (np.arange(64) % 5).astype(np.uint64))   # ties inside every group
+    out = np.zeros_like(x)
+    lib.run("csdu_row64", op, len(x), wpb, x, out)
+    g = 16 if op == 0 else 8
+    want = np.repeat(x.reshape(len(x), 64 // g, g).min(axis=2), g, axis=1)
+    same(f"{['rowmin64', 'halfmin64'][op]} (k_vp8enc.hip) [{wpb * 64} threads]", out, want)
+
+
+# ---------------------------------------------------------------------------------------------------- k_vp8l_refs.hip
+def unit_refs_lanes(lib, op, wpb):
+    x = wave_words()
+    nw = len(x)
+    rng = np.random.default_rng(59)
+    src = rng.integers(-1, 64, (nw, 64)).astype(np.int32)   # -1: the lane itself
+    src[0] = -1
+    src[1] = np.arange(64)[::-1]
+    src[2] = 63
+    src[3] = (np.arange(64) + 32) % 64
+    arg = np.array([(SEAM_LANES + [1, 47])[i % 8] for i in range(nw)], np.int32)
+    out = np.zeros_like(x)
+    lib.run("csdu_refs_lanes", op, nw, wpb, x, src, arg, out)
+    if op == 0:
+        same(f"lget (k_vp8l_refs.hip) [{wpb * 64} threads]: the chosen lane's value, in every lane", out, np.repeat(x[np.arange(nw), arg][:, None], 64, axis=1))
+    else:
+        same(f"lshfl (k_vp8l_refs.hip) [{wpb * 64} threads]: lane l takes lane src[l]'s value, its own where src[l] < 0", out, np.take_along_axis(x, np.where(src < 0, np.arange(64)[None, :], src), axis=1))
+
+
+# ---------------------------------------------------------------------------------------------------- bit readers
+READER_LENS = [3, 4, 255, 256, 257, 513, 1030]   # the unaligned tail of loadw, less than a window of 64 words, one and two refills of the window
+
+
+@functools.lru_cache(None)
+def reader_script():
+    """[(what, n)]: 0 get(n), 1 peek(n), 2 skip(n); every n from 1 to 32 with each, then a seeded mix that runs past the end of the longest buffer"""
+    rng = np.random.default_rng(41)
+    s = [(what, n) for n in range(1, 33) for what in (1, 0, 1, 2)]
+    s += [(int(rng.choice([0, 0, 0, 1, 2, 2])), int(rng.integers(1, 33))) for _ in range(900)]
+    s += [(0, 32), (1, 32), (2, 32), (0, 1)]
+    assert sum(n for what, n in s if what != 1) > (max(READER_LENS) + 8) * 8
+    return s
+
+
+@functools.lru_cache(None)
+def reader_pool(with_seek):
+    """-> pool, off, len, at: a buffer per wave, each on a 16-byte boundary with other data right behind its end (a reader must not look there)"""
+    rng = np.random.default_rng(43)
+    cases = [(n, 0) for n in READER_LENS] + ([(1030, 4), (1030, 5), (1030, 6), (1030, 7), (257, 1), (257, 2), (257, 255), (513, 258), (4, 3)] if with_seek else [(1030, 0)])
+    while len(cases) % 8: cases.append((int(rng.integers(5, 700)), 0))
+    off, at_, len_, total = [], [], [], 0
+    for n, at in cases:
+        off.append(total); len_.append(n); at_.append(at)
+        total += (n + 15) // 16 * 16
+    pool = rng.integers(1, 256, total + 16).astype(np.uint8)   # no zero byte: bits from behind a buffer's end would show
+    return pool, np.array(off, np.uint32), np.array(len_, np.uint32), np.array(at_, np.uint32)
+
+
+def unit_lereader(lib, wpb):
+    """csp::LeReader against the bytes as one little-endian integer: bit i of the stream is bit i of it, and there is nothing but zeros behind the end"""
+    pool, off, ln, at = reader_pool(True)
+    script = reader_script()
+    nw, ns = len(off), len(script)
+    val, pos, over = (np.zeros((nw, ns), np.uint32) for _ in range(3))
+    lib.run("csdu_lereader", nw, wpb, pool, ("z", len(pool)), off, ln, at, np.array(script, np.int32), ns, val, pos, over)
+    wv, wp, wo = np.zeros_like(val), np.zeros_like(pos), np.zeros_like(over)
+    for w in range(nw):
+        big = int.from_bytes(pool[off[w]:off[w] + ln[w]].tobytes(), "little")
+        p = int(at[w]) * 8
+        for i, (what, n) in enumerate(script):
+            if what != 2: wv[w, i] = (big >> p) & ((1 << n) - 1)
+            if what != 1: p += n
+            wp[w, i], wo[w, i] = p >> 3, p > int(ln[w]) * 8
+    name = f"csp::LeReader [{wpb * 64} threads]"
+    same(f"{name}: the bits of get / peek (buffer lengths {ln.tolist()}, started at {at.tolist()})", val, wv)
+    same(f"{name}: byte_pos()", pos, wp)
+    same(f"{name}: overrun(), true exactly once more bits were taken than the buffer holds", over, wo)
+    assert wo.any() and not wo.all()
+
+
+def unit_wavereader(lib, wpb):
+    """WaveReader (k_decode_prog.hip) against the bytes as one big-endian integer, zeros behind the end; peek16() shows the next 16 bits"""
+    pool, off, ln, _ = reader_pool(False)
+    script = reader_script()
+    nw, ns = len(off), len(script)
+    val, over = np.zeros((nw, ns), np.uint32), np.zeros((nw, ns), np.uint32)
+    lib.run("csdu_wavereader", nw, wpb, pool, ("z", len(pool)), off, ln, np.array(script, np.int32), ns, val, over)
+    wv, wo = np.zeros_like(val), np.zeros_like(over)
+    tail = 8 * (sum(n for _, n in script) // 8 + 8)   # zero bits enough for the whole script
+    for w in range(nw):
+        nbits = int(ln[w]) * 8 + tail
+        big = int.from_bytes(pool[off[w]:off[w] + ln[w]].tobytes(), "big") << tail
+        p = 0
+        for i, (what, n) in enumerate(script):
+            take = 16 if what == 1 else n
+            if what != 2: wv[w, i] = (big >> (nbits - p - take)) & ((1 << take) - 1)
+            if what != 1: p += n
+            wo[w, i] = p > int(ln[w]) * 8
+    name = f"WaveReader [{wpb * 64} threads]"
+    same(f"{name}: the bits of get / peek16 (buffer lengths {ln.tolist()})", val, wv)
+    same(f"{name}: insufficient(), true exactly once more bits were taken than the buffer holds", over, wo)
+
+
+# ---------------------------------------------------------------------------------------------------- png_lz.h
+def unit_lz(lib):
+    """load32u / load64u at every misalignment, and align_bytes.  align_bytes' contract: shift <= 3 -- the device instruction takes the low two bits of it, the
+    emulation shifts by 8 * shift as given.  Its call sites (lz_tokenize's fixed distances) pass 2, and 4 - d for d = 1, 2, 3: the shifts 1, 2, 3 run here."""
+    rng = np.random.default_rng(47)
+    n = 256
+    pool = rng.integers(0, 256, n + 7).astype(np.uint8)
+    hi, lo = rng.integers(0, 1 << 32, n).astype(np.uint32), rng.integers(0, 1 << 32, n).astype(np.uint32)
+    shift = (1 + np.arange(n) // 8 % 3).astype(np.uint32)
+    o32, o64, oal = np.zeros(n, np.uint32), np.zeros(n, np.uint64), np.zeros(n, np.uint32)
+    lib.run("csdu_lz", n, pool, hi, lo, shift, o32, o64, oal)
+    raw = pool.tobytes()
+    same("load32u (png_lz.h): four bytes, little-endian, at every misalignment", o32, np.array([int.from_bytes(raw[i:i + 4], "little") for i in range(n)], np.uint32))
+    same("load64u (png_lz.h): eight bytes, little-endian, at every misalignment", o64, np.array([int.from_bytes(raw[i:i + 8], "little") for i in range(n)], np.uint64))
+    want = [(((int(h) << 32) | int(l)) >> (8 * int(s))) & M32 for h, l, s in zip(hi, lo, shift)]
+    same("align_bytes (png_lz.h): bytes shift .. shift + 3 of hi:lo", oal, np.array(want, np.uint32))
+
+
+# ---------------------------------------------------------------------------------------------------- k_png_filter.hip
+def unit_dither_dist(lib):
+    """the dither's squared distance: every wanted colour against real palette entries and against the padding entry 0x40004000 / 0x40004000"""
+    rng = np.random.default_rng(53)
+    corners = np.array([[255 * ((c >> k) & 1) for k in range(4)] for c in range(16)])
+    want4 = np.concatenate([corners, rng.integers(0, 256, (10000, 4))])                       # r, g, b, a in [0, 255]
+    pal = np.concatenate([corners[[0, 15, 5, 10]], rng.integers(0, 256, (4, 4))])             # 8 real entries
+    W, P = np.repeat(want4, len(pal) + 1, axis=0), np.tile(np.concatenate([pal, [[0x4000] * 4]]), (len(want4), 1))
+    pack = lambda a, b: (a | (b << 16)).astype(np.uint32)
+    out = np.zeros(len(W), np.uint32)
+    lib.run("csdu_dither_dist", len(W), pack(W[:, 0], W[:, 1]), pack(W[:, 2], W[:, 3]), pack(P[:, 0], P[:, 1]), pack(P[:, 2], P[:, 3]), out)
+    d = ((W.astype(np.int64) - P.astype(np.int64)) ** 2).sum(axis=1)
+    assert d.max() < 1 << 32                                                                   # no wrap: the comparison below is with the true distance
+    same("dpk_sub + ddot2 as k_png_dither composes them: the squared distance", out, d.astype(np.uint32))
+    per = out.reshape(len(want4), len(pal) + 1).astype(np.int64)
+    assert (per[:, -1:] > per[:, :-1]).all(), "k_png_dither's padding entry is not farther than every real palette entry"
+
+
+# ---------------------------------------------------------------------------------------------------- the list
+def _units():
+    u = {}
+    for nt in (256, 64):
+        for v in range(6): u[f"fdct-{v}-{nt}"] = functools.partial(unit_fdct, variant=v, nthreads=nt)
+        for c in (0, 1): u[f"dering-{c}-{nt}"] = functools.partial(unit_dering, centred=c, nthreads=nt)
+        for c in (0, 1): u[f"idct-{c}-{nt}"] = functools.partial(unit_idct, centred=c, nthreads=nt)
+    for op in range(len(PK_OPS)): u[f"pk-{PK_OPS[op]}"] = functools.partial(unit_pk, op=op)
+    u["pk_abs16"] = unit_pk_abs16
+    for wpb in (1, 4):
+        for op in range(len(WAVE32_OPS)): u[f"{WAVE32_OPS[op]}-{wpb * 64}"] = functools.partial(unit_wave32, op=op, wpb=wpb)
+        for op in range(2): u[f"{['lsum', 'lmin64'][op]}-{wpb * 64}"] = functools.partial(unit_wave64, op=op, wpb=wpb)
+        for op in range(4): u[f"{['rowsum', 'halfsum', 'shfl_row_first', 'shfl_row_ninth'][op]}-{wpb * 64}"] = functools.partial(unit_row32, op=op, wpb=wpb)
+        for op in range(2): u[f"{['rowmin64', 'halfmin64'][op]}-{wpb * 64}"] = functools.partial(unit_row64, op=op, wpb=wpb)
+        for op in range(2): u[f"vp8l_refs_{['lget', 'lshfl'][op]}-{wpb * 64}"] = functools.partial(unit_refs_lanes, op=op, wpb=wpb)
+        u[f"LeReader-{wpb * 64}"] = functools.partial(unit_lereader, wpb=wpb)
+        u[f"WaveReader-{wpb * 64}"] = functools.partial(unit_wavereader, wpb=wpb)
+    for nt in (64, 256):
+        for op in range(3): u[f"{['wave_scan_add', 'wave_scan_or', 'wave_incl_scan'][op]}-{nt}"] = functools.partial(unit_escan, op=op, nthreads=nt)
+        u[f"wave_incl_scan_high_halves-{nt}"] = functools.partial(unit_incl_scan_high_halves, nthreads=nt)
+        u[f"wave_or64-{nt}"] = functools.partial(unit_or64, nthreads=nt)
+    for nt in (64, 65, 96, 256):
+        for op in (3, 4): u[f"{['wave_last', 'wave_last_of_scan'][op - 3]}-{nt}"] = functools.partial(unit_escan, op=op, nthreads=nt)
+    u["load_unaligned_align_bytes"] = unit_lz
+    u["dither_distance"] = unit_dither_dist
+    return u
+
+
+UNITS = _units()

@@ -21,8 +21,10 @@ def lossy_cases(big=False):
              "palette_257_colours", "adam7_RGB_33x21", "RGB_1x1", "RGBA_300x2")
     cases = [c for c in png_cases() if c[0] in names]
     cases.append(("RGBA_soft_alpha", synth_png(71, 120, 90, "RGBA", texture=5.0)))
-    cases.append(("RGB_tall_24x600", synth_png(73, 24, 600, "RGB", texture=4.0)))   # three bands of k_png_dither's 256 rows, the last one short: the error rows handed down through HBM
-    cases.append(("RGB_513_rows", synth_png(74, 9, 513, "RGB", texture=6.0)))         # a band of one row
+    # k_png_dither walks a picture in bands of CSP_DITHER_ROWS = 512 rows; a band hands its last row's error down to the next through one of two line buffers in HBM
+    cases.append(("RGB_tall_24x600", synth_png(73, 24, 600, "RGB", texture=4.0)))   # two bands, the second one short (88 rows)
+    cases.append(("RGB_513_rows", synth_png(74, 9, 513, "RGB", texture=6.0)))         # a second band of one row
+    cases.append(("RGB_1030_rows", synth_png(75, 9, 1030, "RGB", texture=6.0)))       # a full middle band; the third band is the first to read the other line buffer (the two alternate band by band)
     if big:
         cases.append(("RGB_640x480", synth_png(72, 640, 480, "RGB", texture=2.0)))
     return cases
