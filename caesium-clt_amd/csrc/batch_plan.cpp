@@ -236,6 +236,7 @@ PlanSwitches PlanSwitches::read() {
     s.nz_once = !is("CSH_NZ_ONCE", "0");
     s.tr_sort = !is("CSH_TR_SORT", "0");
     s.nz_fused = !is("CSH_NZ_FUSED", "0");
+    s.ref_list = is("CSH_REF_LIST", "1") || (s.ref_list && !is("CSH_REF_LIST", "0"));   // "1" / "0" name the path, anything else leaves the default
     const char *pp = getenv("CSH_PROG_PAR");
     s.prog_par = pp && !strcmp(pp, "0") ? 0 : (pp && !strcmp(pp, "1") ? 1 : -1);
     s.fused_420 = !getenv("CSH_NO_FUSED_420");
@@ -372,10 +373,12 @@ void BatchPlanner::add_works(Item &it, ImgDesc &im, int img_index, const std::ve
         memset(&w, 0, sizeof w);
         w.image = img_index; w.scan = sidx;
         w.out_off = 0xFFFFFFFFu;   // not part of a file until k_layout says so (a conditional stage of the scan search may never run)
-        // progressive AC first-pass scans are coded from the component's compacted list at their Al; everything else from tokens
+        // progressive AC scans are coded from the component's compacted list at their Al: first-pass scans entirely (k_list_stats, k_list_pack), refinement
+        // scans through tokens k_list_refine makes from it (CSH_REF_LIST=0: through k_tokens' kind-0 chunks, from the tiles); everything else from tokens
         const bool from_list = e.Ss > 0 && !e.sequential && e.Ah == 0;
-        w.list = 0xFFFFFFFFu;
-        if (from_list) {
+        const bool ref_list = sw.ref_list && e.Ss > 0 && !e.sequential && e.Ah != 0;
+        w.list = 0xFFFFFFFFu; w.rs_base = 0xFFFFFFFFu;
+        if (from_list || ref_list) {
             if (e.Al >= CSH_NZ_LEVELS) { it.code = CS_ERR_JPEG_FEATURE; it.msg = "internal: output scan script outside what the list coder carries"; }
             else {
                 w.list = nz_list(img_index, e.comp[0], e.Al, im, in_len);
@@ -398,8 +401,9 @@ void BatchPlanner::add_works(Item &it, ImgDesc &im, int img_index, const std::ve
             const uint32_t nch = (w.nunits + 255) / 256;
             w.first_chunk = b->enc.nslots; b->enc.nslots += nch;
             w.hist_row0 = b->enc.hist_rows; b->enc.hist_rows += nch * uint32_t(e.ntables);
-            uint32_t &cursor = w.list != 0xFFFFFFFFu ? b->enc.nlist_slots : b->enc.ntok_slots;
+            uint32_t &cursor = (from_list && w.list != 0xFFFFFFFFu) ? b->enc.nlist_slots : b->enc.ntok_slots;
             w.ls_base = cursor; cursor += nch;
+            if (ref_list && w.list != 0xFFFFFFFFu) { w.rs_base = b->enc.nref_slots; b->enc.nref_slots += nch; }
         }
         if (e.Ss == 0 || e.sequential) {   // DC scans and sequential-mode scans: one token workgroup per (scan, 256 units)
             // tokens of a DC scan are known exactly (one per block, or one per fifteen blocks' bits); a sequential-mode block has at most 64 + 3
@@ -423,13 +427,28 @@ void BatchPlanner::add_works(Item &it, ImgDesc &im, int img_index, const std::ve
         const uint32_t nu = b->enc.nzsets[size_t(si)].nunits;
         for (uint32_t j = 0; levels && j < (nu + 255) / 256; j++) b->enc.nzchunks.push_back(NzChunk{uint32_t(si), j, levels, nz_gate[c]});
     }
-    // the progressive AC refinement scans of a component share one pass over its blocks (k_tokens)
+    // the progressive AC refinement scans of a component share one region of the token pool and (CSH_REF_LIST=0) one pass of k_tokens over its blocks
     for (int c = 0; c < im.ncomp; c++) {
         int nac = 0;
-        for (int sidx : list) { const EncScan &e = b->enc.script[sidx]; if (e.Ss > 0 && !e.sequential && e.Ah && e.comp[0] == c) { nac++; if (e.Al > 3) nac = 99; } }
-        if (nac > CSH_TK_MAXSLOT) { it.code = CS_ERR_JPEG_FEATURE; it.msg = "internal: output scan script outside what the token kernel carries"; }
+        for (int sidx : list) { const EncScan &e = b->enc.script[sidx]; if (e.Ss > 0 && !e.sequential && e.Ah && e.comp[0] == c) { nac++; if (e.Al > 3 && !sw.ref_list) nac = 99; } }
+        // (what a TokPlan carries limits k_tokens' kind-0 chunks only; on the list path a scan outside the list levels has failed its file above and has no slot in ref_slots)
+        const bool too_many = !sw.ref_list && nac > CSH_TK_MAXSLOT;
+        if (too_many) { it.code = CS_ERR_JPEG_FEATURE; it.msg = "internal: output scan script outside what the token kernel carries"; }
         const uint32_t nu = uint32_t(im.out[c].real_bw * im.out[c].real_bh);
-        if (!nac || nac > CSH_TK_MAXSLOT) continue;
+        if (!nac || too_many) continue;
+        // every non-zero coefficient becomes a token in exactly one scan of a script (~5 bits of a source file each), plus an EOB per
+        // block and scan; the search's lists hold several scripts' worth
+        const uint64_t blocks_all = blocks_of(im);
+        const uint64_t scripts = b->enc.search ? uint64_t(nac + 1) / 2 : 1;
+        const uint64_t est = uint64_t(in_len) * 3 * scripts * nu / std::max<uint64_t>(1, blocks_all) + uint64_t(nu) * nac + 1024;
+        if (sw.ref_list) {   // coded from the lists: no plan, no token chunk -- the scans' slots name the component's region themselves
+            for (size_t k = 0; k < list.size(); k++) {
+                const EncScan &e = b->enc.script[list[k]];
+                if (e.Ss > 0 && !e.sequential && e.Ah && e.comp[0] == c && b->enc.swork[size_t(w_first) + k].rs_base != 0xFFFFFFFFu) b->enc.swork[size_t(w_first) + k].region = uint32_t(b->enc.region_est.size());
+            }
+            b->enc.region_est.push_back(stats_only ? 64u : uint32_t(std::min<uint64_t>(est, 0x3FFFFFFFu)));
+            continue;
+        }
         TokPlan P;
         memset(&P, 0, sizeof P);
         P.nunits = nu; P.real_bw = im.out[c].real_bw; P.bw = im.out[c].bw; P.tile_base = im.out[c].tile_base;   // tile_base of re-quantised tiles is rebased below
@@ -443,11 +462,6 @@ void BatchPlanner::add_works(Item &it, ImgDesc &im, int img_index, const std::ve
             a.unit_base = w.unit_base; a.word_base = w.word_base; a.first_chunk = w.first_chunk; a.table_base = w.table_base; a.nunits_work = w.nunits; a.corr_base = w.corr_base;
             a.Ss = uint8_t(e.Ss); a.Se = uint8_t(e.Se); a.Ah = uint8_t(e.Ah); a.Al = uint8_t(e.Al);
         }
-        // every non-zero coefficient becomes a token in exactly one scan of a script (~5 bits of a source file each), plus an EOB per
-        // block and scan; the search's lists hold several scripts' worth
-        const uint64_t blocks_all = blocks_of(im);
-        const uint64_t scripts = b->enc.search ? uint64_t(nac + 1) / 2 : 1;
-        const uint64_t est = uint64_t(in_len) * 3 * scripts * nu / std::max<uint64_t>(1, blocks_all) + uint64_t(nu) * nac + 1024;
         for (uint32_t j = 0; j < (nu + 255) / 256; j++) b->enc.echunks.push_back(EChunk{uint32_t(img_index), uint16_t(c), 0, j, uint32_t(b->enc.plans.size()), uint32_t(b->enc.region_est.size())});
         b->enc.region_est.push_back(stats_only ? 64u : uint32_t(std::min<uint64_t>(est, 0x3FFFFFFFu)));
         b->enc.plan_comp.push_back(c); b->enc.plan_image.push_back(img_index);
@@ -1143,7 +1157,7 @@ int BatchPlanner::upload(Laps &laps) {
         b->enc.d_tok_off.alloc(4 * size_t(b->enc.nslots) + 4) || b->enc.d_chunk_ntok.alloc(4 * size_t(b->enc.nslots) + 4) || b->enc.d_slot_hist.alloc(size_t(b->enc.hist_rows) * 256 + 256) ||
         b->enc.d_slot_raw.alloc(size_t(b->enc.nslots) + 1) || b->enc.d_img_list.upload(b->enc.img_list, st) || b->enc.d_img_nlist.upload(b->enc.img_nlist, st) || b->enc.d_scan_cost.alloc(b->enc.swork.size() + 1) || b->enc.d_slot_eobh.alloc(16 * size_t(b->enc.nslots) + 16) || b->enc.d_chunk_bits.alloc(size_t(b->enc.nslots) + 1) || b->enc.d_chunk_off.alloc(size_t(b->enc.nslots) + 2) || b->enc.d_tok_cursor.alloc(b->enc.region_est.size() + 1) || b->enc.d_regions.upload(b->enc.regions, st) ||
         b->enc.d_tables.alloc(b->enc.ntables) || b->enc.d_scan_pad.alloc(b->enc.swork.size() + 1) ||
-        b->enc.d_nzlists.upload(b->enc.nzlists, st) || b->enc.d_nzsets.upload(b->enc.nzsets, st) || b->enc.d_nzchunks.upload(b->enc.nzchunks, st) || (b->enc.n_fused && b->enc.d_nzchunks_fused.upload(b->enc.nzchunks_fused, st)) || b->enc.d_list_slots.alloc(size_t(b->enc.nlist_slots) + 1) || b->enc.d_tok_slots.alloc(size_t(b->enc.ntok_slots) + 1) ||
+        b->enc.d_nzlists.upload(b->enc.nzlists, st) || b->enc.d_nzsets.upload(b->enc.nzsets, st) || b->enc.d_nzchunks.upload(b->enc.nzchunks, st) || (b->enc.n_fused && b->enc.d_nzchunks_fused.upload(b->enc.nzchunks_fused, st)) || b->enc.d_list_slots.alloc(size_t(b->enc.nlist_slots) + 1) || b->enc.d_tok_slots.alloc(size_t(b->enc.ntok_slots) + 1) || b->enc.d_ref_slots.alloc(size_t(b->enc.nref_slots) + 1) ||
         b->enc.d_nz_cursor.alloc(b->enc.nzlists.size() + 1) || b->enc.d_nz_chunk_off.alloc(size_t(b->enc.nz_nrec) + 1) || b->enc.d_nz_chunk_cnt.alloc(size_t(b->enc.nz_nrec) + 1) ||
         b->enc.d_scan_raw_off.alloc(b->enc.swork.size() + 2) || b->out.d_img_size.alloc(b->nimg + 1) || b->out.d_img_size_pad.alloc(b->nimg + 1) ||
         b->out.d_img_off.alloc(b->nimg + 2) || b->out.d_status.alloc(b->nimg) || b->out.d_overflow.alloc(4))
@@ -1151,7 +1165,7 @@ int BatchPlanner::upload(Laps &laps) {
     // the slots of every work item, written where they are used (the host counted them: add_works)
     if (hipMemsetAsync(b->enc.d_slots.p, 0, (size_t(b->enc.nslots) + 1) * sizeof(SlotRec), st) != hipSuccess ||
         hipMemsetAsync(b->enc.d_slot_work.p, 0, (size_t(b->enc.nslots) + 1) * sizeof(uint32_t), st) != hipSuccess) { csh_set_error("hipMemsetAsync failed"); return CS_ERR_NO_DEVICE; }
-    launch_make_slots(st, b->enc.d_swork.p, uint32_t(b->enc.swork.size()), b->enc.d_script.p, b->enc.d_nzlists.p, b->enc.d_slots.p, b->enc.d_slot_work.p, b->enc.d_list_slots.p, b->enc.d_tok_slots.p);
+    launch_make_slots(st, b->enc.d_swork.p, uint32_t(b->enc.swork.size()), b->enc.d_script.p, b->enc.d_nzlists.p, b->enc.d_slots.p, b->enc.d_slot_work.p, b->enc.d_list_slots.p, b->enc.d_tok_slots.p, b->enc.d_ref_slots.p);
     if (b->tr.trellis && (b->tr.d_trows.upload(b->tr.trows, st) || (b->tr.t_sort && (b->tr.d_tperm.alloc(size_t(b->tr.t_units) + 1) || b->tr.d_tblk_cnt.alloc(size_t(b->tr.t_units) + 1) || (b->tr.nz_once && b->tr.d_tblk_off.alloc(size_t(b->tr.t_units) + 1)))))) return CS_ERR_NO_DEVICE;
     if (b->tr.trellis && (b->tr.d_twork.upload(b->tr.twork, st) || b->tr.d_truns.upload(b->tr.truns, st) || b->tr.d_tqueue.alloc(1) || b->tr.d_tlambda.alloc(size_t(b->tr.t_units) + 1) || b->tr.d_tdcbt.alloc(size_t(b->tr.t_units) + 1) ||
                        b->tr.d_tspill.alloc(trellis_spill_words(trellis_ac_slots())) || b->pix.d_dct_raw.alloc(size_t(b->ntiles_out) * CSH_TILE_I16)))

@@ -281,6 +281,7 @@ struct Run {
         c.nzchunks = (fused ? b->enc.d_nzchunks_fused.p : b->enc.d_nzchunks.p) + sg.nzc0; c.nnzchunks = sg.nnzc;
         c.nz_build = sg.nz_build[fused ? 1 : 0]; c.nz_filter = sg.nz_filter[fused ? 1 : 0];
         c.list_slots = b->enc.d_list_slots.p + sg.ls0; c.nlist_slots = sg.nls; c.tok_slots = b->enc.d_tok_slots.p + sg.ts0; c.ntok_slots = sg.nts;
+        c.ref_slots = b->enc.d_ref_slots.p + sg.rs0; c.nref_slots = sg.nrs;
     }
 
     // ---- mozjpeg's trellis quantiser (CSH_PROFILE=mozjpeg): per component a statistics scan over the scalar-quantised coefficients
@@ -328,7 +329,10 @@ struct Run {
         if (b->enc.d_long_cnt.zero(st)) return -1;
         launch_nzlist(st, c);       // the lists this stage's first-pass scans are coded from and no earlier stage made
         SMARK(KS_NZLIST);
-        launch_tokens(st, c);       // DC, sequential-mode and refinement scans
+        launch_list_refine(st, c);  // AC refinement scans, from the lists (timed with k_tokens, whose kind-0 chunks they were)
+        for (uint32_t wi = sg.work0; sg.nrs && wi < sg.work0 + sg.nwork; wi++)
+            if (b->enc.swork[wi].rs_base != 0xFFFFFFFFu && (!gate || b->enc.work_active[wi])) b->enc.last_run_refine++;
+        launch_tokens(st, c);       // DC and sequential-mode scans (CSH_REF_LIST=0: the refinement scans too, from the tiles)
         SMARK(KS_TOKENS);
         launch_list_stats(st, c);   // AC first-pass scans
         SMARK(KS_LIST_STATS);
@@ -433,7 +437,7 @@ struct Run {
 
 int run_once(csh_batch *b, csh_timing *t, bool requant_only) {
     Run r(b, t);
-    b->enc.last_run_fused = 0;
+    b->enc.last_run_fused = 0; b->enc.last_run_refine = 0;
     if (r.pools() || r.marks.start()) return -1;
     // a re-run at another quality (size targeting): from the retained DCT -- unless the batch derings: the overshoot mozjpeg's deringing allows
     // depends on the DC quantiser (jcdctmgr.c preprocess_deringing), so the forward DCT's input changes with the table and the re-run starts

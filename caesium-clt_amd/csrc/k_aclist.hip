@@ -1,4 +1,5 @@
-// k_aclist.hip -- progressive AC scans coded from COMPACTED COEFFICIENT LISTS (first-pass scans: Ah = 0).
+// k_aclist.hip -- progressive AC scans coded from COMPACTED COEFFICIENT LISTS: the first-pass scans (Ah = 0) entirely, the refinement scans
+// (Ah = Al + 1) up to their tokens (k_list_refine, at the end of the file; CSH_REF_LIST=0 leaves them to k_tokens).
 //
 // Replaces, for those scans, the per-block sweeps of k_entropy.hip's k_tokens and the token stream between it and k_pack (mozjpeg
 // jcphuff.c encode_mcu_AC_first + jchuff.c statistics, reached from /root/reference/src/compressor.rs:305).
@@ -459,6 +460,224 @@ __global__ void __launch_bounds__(256) k_list_pack(EncCtx c) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ refinement scans (Ah = Al + 1)
+// A refinement scan is a flat walk over the component's level-Al list too: an entry of magnitude 1 (after >> Al) is a newly significant
+// coefficient (N), one of magnitude >= 2 a coefficient with history (H) whose bit 0 is its correction bit; no tile is read, no bit plane made,
+// and no lane walks a block by itself.  What k_tokens' kind-0 chunks made for such a scan (k_entropy.hip emit_ac_refine, refine_room,
+// correction_word: the specification) comes out of k_list_refine, ONE WAVE per (scan, chunk) slot, four entries per lane and step:
+//   per entry, segmented by the blocks' END entries and carried across the steps:
+//     hex   H entries of the block in front of it (its correction bit is bit 63 - hex of the block's correction word)
+//     z     zeros of the band in front of it:  k - Ss - (N and H entries of the block in front of it)
+//     zp    z of the block's previous N (0: none): the zero run of the entry is z - zp
+//     zq    z of the entry in front of it in the block's band (0: none)
+//   a ZRL is due whenever sixteen more zeros of a gap have gone by, at the next entry of the gap -- and only in gaps an N closes (k <= the
+//   block's last N): entry e emits ((z - zp) >> 4) - ((zq - zp) >> 4) of them, an N then its own token with run (z - zp) & 15.  The correction
+//   bits a token takes along are those since the block's last emitting entry (jcphuff.c: they ride behind the next symbol): hex - cur for the
+//   first token of an entry, none for further ones.  The block's END entry is its EOB (unless an N sits at Se), with the H entries left.
+// Pass 1 takes everything but the tokens -- histogram, correction words, tails, flags, raw bits, the number of tokens -- and leaves per block
+// its last N and its H count in LDS; pass 2 reads the chunk again (out of the L2) and writes the tokens behind one atomic add on the region's
+// cursor.  All of a slot's tokens are its segment 0 (k_pack walks the four segments as one list).
+struct RefCarry { uint32_t runH, runN, base, prevN, prevNZ; };
+__device__ __forceinline__ static uint32_t ref_isN(uint32_t e, uint32_t Ss, uint32_t Se) { const uint32_t k = e & 127u; return (k >= Ss && k <= Se && ((e >> 8) & 0x7FFFu) == 1u) ? 1u : 0u; }
+__device__ __forceinline__ static uint32_t ref_isH(uint32_t e, uint32_t Ss, uint32_t Se) { const uint32_t k = e & 127u; return (k >= Ss && k <= Se && ((e >> 8) & 0x7FFFu) >= 2u) ? 1u : 0u; }
+__device__ __forceinline__ static uint32_t ref_same(uint32_t key, uint32_t blk) { return (key >> 6) == blk + 1u ? (key & 63u) : 0u; }   // the value of a (block + 1) << 6 | value key, if it is of this block
+// one step's entries e[q][l] -> hex, z, zp, and with WITH_ZQ (pass 2) zq -- pass 1 hands in an array that is neither read nor written;
+// entries that are neither N nor H get values nobody reads
+template <bool WITH_ZQ>
+__device__ __forceinline__ static void ref_step(const LV<uint32_t> (&e)[4], uint32_t Ss, uint32_t Se, RefCarry &C, LV<uint32_t> (&hex)[4], LV<uint32_t> (&z)[4], LV<uint32_t> (&zp)[4],
+                                                LV<uint32_t> (&zq)[4]) {
+    LV<uint32_t> cnt;
+    LFOR(l) {
+        uint32_t s = 0;
+        CSH_UNROLL
+        for (int q = 0; q < 4; q++) s += ref_isH(e[q][l], Ss, Se) | (ref_isN(e[q][l], Ss, Se) << 16);
+        cnt[l] = s;
+    }
+    uint32_t tot;
+    const LV<uint32_t> ex = lscan(cnt, tot);   // (a step has 256 entries: the halves do not meet)
+    // where the block started: the H and N counts at the last END in front of the entry (a chunk has < 2^14 entries)
+    LV<uint32_t> kb[4];
+    LFOR(l) {
+        uint32_t ph = C.runH + (ex[l] & 0xFFFFu), pn = C.runN + (ex[l] >> 16);
+        CSH_UNROLL
+        for (int q = 0; q < 4; q++) {
+            kb[q][l] = (e[q][l] & CSH_NZ_END) ? ((ph << 14) | pn) + 1u : 0u;
+            hex[q][l] = ph; z[q][l] = pn;   // for now: the counts from the chunk's start
+            ph += ref_isH(e[q][l], Ss, Se); pn += ref_isN(e[q][l], Ss, Se);
+        }
+    }
+    C.runH += tot & 0xFFFFu; C.runN += tot >> 16;
+    lscan_last4(kb, C.base);
+    LFOR(l) {
+        CSH_UNROLL
+        for (int q = 0; q < 4; q++) {
+            const uint32_t b = kb[q][l] ? kb[q][l] - 1u : 0u, blk = (e[q][l] >> 23) & 255u, nz = ref_isH(e[q][l], Ss, Se) | ref_isN(e[q][l], Ss, Se);
+            const uint32_t h = hex[q][l] - (b >> 14), n = z[q][l] - (b & 0x3FFFu);
+            hex[q][l] = h;
+            z[q][l] = nz ? (e[q][l] & 127u) - Ss - h - n : 0u;   // <= 62
+            const uint32_t key = ((blk + 1u) << 6) | z[q][l];
+            zp[q][l] = ref_isN(e[q][l], Ss, Se) ? key : 0u;
+            if (WITH_ZQ) zq[q][l] = nz ? key : 0u;
+        }
+    }
+    lscan_last4(zp, C.prevN);
+    if (WITH_ZQ) lscan_last4(zq, C.prevNZ);
+    LFOR(l) {
+        CSH_UNROLL
+        for (int q = 0; q < 4; q++) {
+            const uint32_t blk = (e[q][l] >> 23) & 255u;
+            zp[q][l] = ref_same(zp[q][l], blk);
+            if (WITH_ZQ) zq[q][l] = ref_same(zq[q][l], blk);
+        }
+    }
+}
+__global__ void __launch_bounds__(256) k_list_refine(EncCtx c) {
+    CSH_SHARED uint32_t s_hist[4][4][256];   // four copies, lane & 3 (k_list_stats)
+    CSH_SHARED uint32_t s_lastn[4][256];     // per block: its last N, k << 6 | hex (0: no N)
+    CSH_SHARED uint32_t s_nh[4][256];        // per block: its H entries
+    CSH_SHARED uint32_t s_corr[4][256][2];   // per block: its correction word, high half first
+    const int wv = lwave();
+    const uint32_t idx = blockIdx.x * 4u + uint32_t(wv);
+    if (idx >= c.nref_slots) return;
+    const uint32_t cs = c.ref_slots[idx];
+    const SlotRec r = c.slots[cs];
+    if (c.work_active && !c.work_active[r.work]) return;
+    const ListSlot ls = list_of_slot(c, r);
+    uint32_t *hist = &s_hist[wv][0][0], *lastn = s_lastn[wv], *nh = s_nh[wv], *corr = &s_corr[wv][0][0];
+    LFOR(l) {
+        for (int i = l; i < 1024; i += 64) hist[i] = 0u;
+        for (int i = l; i < 256; i += 64) { lastn[i] = 0u; nh[i] = 0u; corr[2 * i] = 0u; corr[2 * i + 1] = 0u; }
+    }
+    CSP_WAVE_SYNC();
+    const uint32_t Ss = r.Ss, Se = r.Se;
+    // ---- pass 1
+    RefCarry C;
+    C.runH = C.runN = C.base = C.prevN = C.prevNZ = 0u;
+    LV<uint32_t> ntok;
+    LFOR(l) ntok[l] = 0u;
+    {
+        LV<uint32_t> x[4];   // the next step's entries, asked for a step ahead
+        LFOR(l) list_load4(ls, 4u * uint32_t(l), x[0][l], x[1][l], x[2][l], x[3][l]);
+        for (uint32_t g0 = 0; g0 < ls.n; g0 += 256) {
+            LV<uint32_t> e[4], hex[4], z[4], zp[4], zq[4];
+            LFOR(l) { e[0][l] = x[0][l]; e[1][l] = x[1][l]; e[2][l] = x[2][l]; e[3][l] = x[3][l]; }
+            if (g0 + 256u < ls.n) LFOR(l) list_load4(ls, g0 + 256u + 4u * uint32_t(l), x[0][l], x[1][l], x[2][l], x[3][l]);
+            ref_step<false>(e, Ss, Se, C, hex, z, zp, zq);
+            LFOR(l) {
+                uint32_t *h = hist + 256 * (l & 3);
+                CSH_UNROLL
+                for (int q = 0; q < 4; q++) {
+                    const uint32_t v = e[q][l], blk = (v >> 23) & 255u;
+                    if (ref_isH(v, Ss, Se)) {
+                        atomicMax(&nh[blk], hex[q][l] + 1u);
+                        if (v & 0x100u) atomicOr(&corr[2u * blk + (hex[q][l] >> 5)], 0x80000000u >> (hex[q][l] & 31u));
+                    } else if (ref_isN(v, Ss, Se)) {
+                        const uint32_t zr = z[q][l] - zp[q][l];
+                        atomicMax(&lastn[blk], ((v & 127u) << 6) | hex[q][l]);
+                        atomicAdd(&h[((zr & 15u) << 4) | 1u], 1u);
+                        if (zr >> 4) atomicAdd(&h[0xF0], zr >> 4);
+                        ntok[l] += 1u + (zr >> 4);
+                    }
+                }
+            }
+        }
+    }
+    CSP_WAVE_SYNC();
+    // the blocks' ends: EOB tokens, tails, correction words, flags (lane = block bit, so the chunk's flags ARE four words of the scan's bit vectors)
+    for (uint32_t w4 = 0; w4 < 4; w4++) {
+        LFOR(l) {
+            const uint32_t i = 64u * w4 + uint32_t(l);
+            if (i < r.nun) {
+                const uint32_t ln = lastn[i];
+                if (ls.n && (ln >> 6) != Se) ntok[l] += 1u;   // (no entries: the list had no room, the run is repeated)
+                c.tail[r.unit0 + i] = uint8_t(nh[i] - (ln & 63u));   // the H entries behind the last N; all of them if there is no N
+                c.corr[r.corr0 + i] = (uint64_t(corr[2u * i]) << 32) | corr[2u * i + 1u];
+            }
+        }
+        const uint64_t ms = lballot([&](int j) { const uint32_t i = 64u * w4 + uint32_t(j); return i < r.nun && lastn[i] != 0u; });
+        const uint64_t me = lballot([&](int j) { const uint32_t i = 64u * w4 + uint32_t(j); return i < r.nun && (lastn[i] >> 6) != Se; });
+        LFOR(l) if (l == 0 && r.j * 4u + w4 < ((r.nunits_work + 63u) >> 6)) { c.sym_bits[r.word_base + r.j * 4u + w4] = ms; c.eob_bits[r.word_base + r.j * 4u + w4] = me; }
+    }
+    const uint32_t total = lsum32(ntok);
+    LFOR(l) {
+        for (int i = l; i < 256; i += 64) {
+            const uint32_t v = hist[i] + hist[256 + i] + hist[512 + i] + hist[768 + i];
+            c.slot_hist[size_t(r.hist_row) * 256u + uint32_t(i)] = uint16_t(v);
+            if (v) atomicAdd(&c.tables[r.table_base].freq[i], v);
+        }
+        if (l == 0) c.slot_raw[cs] = C.runN + C.runH;   // a sign bit per new coefficient, a correction bit per old one
+    }
+    if (c.stats_only) return;   // (nothing is written to the pool)
+    // ---- room in the pool: one atomic add on the region's cursor
+    const TokRegion rg = c.regions[r.region];
+    uint32_t rel = 0;
+    LFOR(l) if (l == 0) rel = atomicAdd(&c.tok_cursor[r.region], total);
+    rel = uni(rel);
+    const bool ok = uint64_t(rel) + total <= rg.cap;
+    LFOR(l) {
+        if (l < 4) { c.tok_off[cs * 4u + uint32_t(l)] = rg.base + rel; c.chunk_ntok[cs * 4u + uint32_t(l)] = (ok && l == 0) ? total : 0u; }
+        if (l == 0 && !ok) c.overflow[1] = 1;
+    }
+    if (!ok) return;
+    uint32_t *tk = c.tokens + rg.base + rel;
+    // (both passes derive the counts from the same entries, so pass 2 writes exactly `total` tokens: `o < total` below cannot fail -- it is there so that a
+    // disagreement could never store outside the reserved room; the emulation build stops on one instead of dropping tokens)
+    // ---- pass 2: the tokens
+    C.runH = C.runN = C.base = C.prevN = C.prevNZ = 0u;
+    uint32_t curc = 0, at = 0;
+    for (uint32_t g0 = 0; g0 < ls.n; g0 += 256) {
+        LV<uint32_t> e[4], hex[4], z[4], zp[4], zq[4], cur[4], nt;
+        LFOR(l) list_load4(ls, g0 + 4u * uint32_t(l), e[0][l], e[1][l], e[2][l], e[3][l]);
+        ref_step<true>(e, Ss, Se, C, hex, z, zp, zq);
+        // zq <- the entry's ZRLs | its tokens << 8;  cur: the key of an emitting entry
+        LFOR(l) {
+            uint32_t s = 0;
+            CSH_UNROLL
+            for (int q = 0; q < 4; q++) {
+                const uint32_t v = e[q][l], blk = (v >> 23) & 255u, lastk = lastn[blk] >> 6, isN = ref_isN(v, Ss, Se);
+                uint32_t nz = 0, n = 0;
+                if ((isN | ref_isH(v, Ss, Se)) && (v & 127u) <= lastk) { nz = ((z[q][l] - zp[q][l]) >> 4) - ((zq[q][l] - zp[q][l]) >> 4); n = nz + isN; }
+                cur[q][l] = n ? ((blk + 1u) << 6) | hex[q][l] : 0u;
+                if ((v & CSH_NZ_END) && lastk != Se) n = 1u;
+                zq[q][l] = nz | (n << 8);
+                s += n;
+            }
+            nt[l] = s;
+        }
+        lscan_last4(cur, curc);
+        uint32_t tot;
+        const LV<uint32_t> ex = lscan(nt, tot);
+        LFOR(l) {
+            uint32_t o = at + ex[l];
+            CSH_UNROLL
+            for (int q = 0; q < 4; q++) {
+                const uint32_t v = e[q][l], blk = (v >> 23) & 255u, nz = zq[q][l] & 255u, n = zq[q][l] >> 8;
+                if (!n) continue;
+                const uint32_t cu = ref_same(cur[q][l], blk);
+                if (v & CSH_NZ_END) {
+                    if (o < total) tk[o] = TK_EOB | (blk << 3) | ((nh[blk] - cu) << 16) | (cu << 22);
+                    o++;
+                    continue;
+                }
+                // the first token takes the correction bits since the block's last emitting entry, the others none
+                uint32_t cnt = hex[q][l] - cu, from = cu;
+                for (uint32_t t = 0; t < nz; t++) {
+                    if (o < total) tk[o] = TK_REF | (blk << 3) | (cnt << 16) | (from << 22) | (1u << 28);
+                    o++; cnt = 0u; from = hex[q][l];
+                }
+                if (n > nz) {
+                    if (o < total) tk[o] = TK_REF | (blk << 3) | (((z[q][l] - zp[q][l]) & 15u) << 11) | ((v & 128u) ? 0u : (1u << 15)) | (cnt << 16) | (from << 22);
+                    o++;
+                }
+            }
+        }
+        at += tot;
+    }
+#ifdef CSH_EMUL
+    if (at != total) { fprintf(stderr, "k_list_refine: pass 2 made %u tokens, pass 1 counted %u\n", at, total); abort(); }
+#endif
+}
+
 __global__ void k_reset_works(ScanWork *work, int nwork) {
     const int j = int(blockIdx.x * blockDim.x + threadIdx.x);
     if (j >= nwork) return;
@@ -471,30 +690,34 @@ void launch_nzlist(hipStream_t st, const EncCtx &c) {
     if (c.nz_filter) CSH_LAUNCH(k_nzfilter, dim3(c.nnzchunks), dim3(CSP_WAVE_THREADS), st, c);
 }
 void launch_list_stats(hipStream_t st, const EncCtx &c) { if (c.nlist_slots) CSH_LAUNCH(k_list_stats, dim3((c.nlist_slots + 3) / 4), dim3(4 * CSP_WAVE_THREADS), st, c); }
+void launch_list_refine(hipStream_t st, const EncCtx &c) { if (c.nref_slots) CSH_LAUNCH(k_list_refine, dim3((c.nref_slots + 3) / 4), dim3(4 * CSP_WAVE_THREADS), st, c); }
 void launch_list_pack(hipStream_t st, const EncCtx &c) { if (c.nlist_slots) CSH_LAUNCH(k_list_pack, dim3((c.nlist_slots + 3) / 4), dim3(4 * CSP_WAVE_THREADS), st, c); }
 // ---- the slots of the work items: one workgroup per work item, one lane per 256-unit chunk.  Under the scan search a 1080p image has ~3.9 k slots in 58 work
 // items: built on the host they were 64 MB of records per 256 files to write and to upload in front of the first kernel (the boundary call paid ~15 ms of
 // every 50 for them); the host only counts them now (batch_plan.cpp add_works).  Slots between the stages belong to no work item and stay zero.
 __global__ void __launch_bounds__(64) k_make_slots(const ScanWork *works, uint32_t nworks, const EncScan *script, const NzList *nzlists, SlotRec *slots, uint32_t *slot_work, uint32_t *list_slots,
-                                                   uint32_t *tok_slots) {
+                                                   uint32_t *tok_slots, uint32_t *ref_slots) {
     const uint32_t wi = blockIdx.x;
     if (wi >= nworks) return;
     const ScanWork &w = works[wi];
     const EncScan &e = script[w.scan];
     const uint32_t nch = (w.nunits + 255u) / 256u;
-    const bool prog_ac = e.Ss > 0 && !e.sequential, listed = w.list != 0xFFFFFFFFu;
+    const bool prog_ac = e.Ss > 0 && !e.sequential, has_list = w.list != 0xFFFFFFFFu;
+    const bool ref_list = has_list && prog_ac && e.Ah;   // a refinement scan coded from its list: k_list_refine makes its tokens, k_pack packs them
+    const bool listed = has_list && !ref_list;
     for (uint32_t j = threadIdx.x; j < nch; j += blockDim.x) {
         SlotRec r;
         r.work = wi; r.j = j; r.nch = nch; r.first_chunk = w.first_chunk; r.unit0 = w.unit_base + 256u * j;
         r.nun = w.nunits - 256u * j < 256u ? w.nunits - 256u * j : 256u; r.table_base = w.table_base; r.ntables = uint16_t(e.ntables);
-        r.flags = uint16_t((prog_ac ? 1 : 0) | (prog_ac && e.Ah ? 2 : 0) | (listed ? 4 : 0));
+        r.flags = uint16_t((prog_ac ? 1 : 0) | (prog_ac && e.Ah ? 2 : 0) | (listed ? 4 : 0) | (ref_list ? 8 : 0));
         r.hist_row = w.hist_row0 + j * uint32_t(e.ntables);
         r.word_base = w.word_base; r.unit_base = w.unit_base; r.nunits_work = w.nunits;
         r.Ss = uint8_t(e.Ss); r.Se = uint8_t(e.Se); r.Ah = uint8_t(e.Ah); r.Al = uint8_t(e.Al); r.corr0 = w.corr_base == 0xFFFFFFFFu ? 0u : w.corr_base + 256u * j;
-        r.nzlist = listed ? w.list : 0u; r.nzrec = listed ? nzlists[w.list].chunk0 + j : 0u;
+        r.nzlist = has_list ? w.list : 0u; r.nzrec = has_list ? nzlists[w.list].chunk0 + j : 0u; r.region = ref_list ? w.region : 0u;
         slots[w.first_chunk + j] = r;
         slot_work[w.first_chunk + j] = wi;
         (listed ? list_slots : tok_slots)[w.ls_base + j] = w.first_chunk + j;
+        if (ref_list) ref_slots[w.rs_base + j] = w.first_chunk + j;
     }
 }
 // the scan search re-points work items to the lists of the point transform it chose (scan_search.cpp search_decide): their slots follow
@@ -510,9 +733,9 @@ void launch_rebind_slots(hipStream_t st, const ScanWork *works, uint32_t nworks,
     if (nworks) CSH_LAUNCH(k_rebind_slots, dim3(nworks), dim3(64), st, works, nworks, nzlists, slots);
 }
 void launch_make_slots(hipStream_t st, const ScanWork *works, uint32_t nworks, const EncScan *script, const NzList *nzlists, SlotRec *slots, uint32_t *slot_work, uint32_t *list_slots,
-                       uint32_t *tok_slots) {
+                       uint32_t *tok_slots, uint32_t *ref_slots) {
     if (!nworks) return;
-    CSH_LAUNCH(k_make_slots, dim3(nworks), dim3(64), st, works, nworks, script, nzlists, slots, slot_work, list_slots, tok_slots);
+    CSH_LAUNCH(k_make_slots, dim3(nworks), dim3(64), st, works, nworks, script, nzlists, slots, slot_work, list_slots, tok_slots, ref_slots);
 }
 
 void launch_reset_works(hipStream_t st, ScanWork *work, int nwork) { if (nwork) CSH_LAUNCH(k_reset_works, dim3((nwork + 255) / 256), dim3(256), st, work, nwork); }

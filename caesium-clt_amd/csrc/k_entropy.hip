@@ -4,6 +4,11 @@
 // jpeg_gen_optimal_table for libcaesium's JPEG path (reference call site
 // /root/reference/src/compressor.rs:305).
 //
+// Which scans come through here: DC and sequential-mode scans (k_tokens' kind-1 chunks) always; the progressive AC first-pass scans never (k_aclist.hip
+// codes them from the compacted coefficient lists); the AC refinement scans only under CSH_REF_LIST=0 (k_tokens' kind-0 chunks, below) -- by default
+// k_list_refine (k_aclist.hip) makes their tokens, correction words, flags and histograms from the lists, and emit_ac_refine / refine_room /
+// correction_word here are the statement of what it must produce.  k_ac_runs, k_gen_tables, k_chunk_sizes and k_pack serve both.
+//
 // Formulation (DESIGN.md "Entropy encode"): the coefficient planes are read ONCE.  k_tokens gives a workgroup 256 consecutive
 // blocks of one component; a lane holds its block's 64 coefficients in registers, derives the per-block bit planes
 // (bit k: |c_k| >= 2^l, bit l of |c_k|, sign) and codes EVERY AC scan of the component from them:
@@ -32,7 +37,7 @@ namespace csh {
 //                                              [27:22] where they start in the unit's correction word  [28] 1 = the event is a ZRL (no sign bit)
 //   EOB  the block ends with an EOB here:      [10:3] unit inside the chunk  [21:16] / [27:22] its trailing correction bits, as in REF;
 //                                              the packer emits the unit's EOBRUN symbol in front of them (eobrun[unit], if it owns one)
-enum : uint32_t { TK_SYM = 0u, TK_RAW = 1u, TK_ACF = 2u, TK_REF = 3u, TK_EOB = 4u };
+// (the kinds' numbers: kernels.h -- k_list_refine of k_aclist.hip writes REF and EOB tokens too)
 #define CSH_PK_WORDS 1024   // the packer's window of the bit stream, per wave, in LDS words (a step of 256 tokens adds at most 768)
 
 __device__ __forceinline__ static uint64_t band_mask(int Ss, int Se) { return (~0ull >> (63 - Se)) & (~0ull << Ss); }

@@ -73,7 +73,7 @@ void launch_refine_chains(hipStream_t st, const uint8_t *clean, const ParScan *p
 // per (work item, 256-unit chunk): SlotRec, slot -> work item, and the slot's entry in the list-coded / token-coded slot lists (k_aclist.hip)
 void launch_rebind_slots(hipStream_t st, const ScanWork *works, uint32_t nworks, const NzList *nzlists, SlotRec *slots);   // after the host re-points work items' lists
 void launch_make_slots(hipStream_t st, const ScanWork *works, uint32_t nworks, const EncScan *script, const NzList *nzlists, SlotRec *slots, uint32_t *slot_work, uint32_t *list_slots,
-                       uint32_t *tok_slots);
+                       uint32_t *tok_slots, uint32_t *ref_slots);
 void launch_decode_prog(hipStream_t st, const uint8_t *clean, const ParScan *pss, const ParHuffSet *huffs, const DecScan *scans, const ProgChain *chains,
                         const int *chain_scans, int nchains, const ImgDesc *imgs, int16_t *coef, uint32_t *need_seq);
 void launch_dec_mark_pending(hipStream_t st, const ParScan *ps, uint32_t total_sub, const uint64_t *list_in, const uint32_t *cnt_in, uint32_t *scan_pending);
@@ -170,8 +170,11 @@ struct EncCtx {  // device pointers + sizes every entropy kernel needs
     uint32_t nlist_slots;
     const uint32_t *tok_slots; // ... and those packed from tokens (k_pack); null: every slot of [slot0, slot0 + nslots)
     uint32_t ntok_slots;
+    const uint32_t *ref_slots; // those of the token-coded slots that are refinement scans coded from their list: k_list_refine writes their tokens (k_tokens does not)
+    uint32_t nref_slots;
     uint32_t nz_build, nz_filter; // the run's NzChunks: some asks for level 0 from the tiles (k_nzlist) / for a filtered level (k_nzfilter); a kernel nobody asks for is not launched
 };
+enum : uint32_t { TK_SYM = 0u, TK_RAW = 1u, TK_ACF = 2u, TK_REF = 3u, TK_EOB = 4u };   // token kinds (bits 0-2 of a token; the fields: k_entropy.hip)
 void launch_tokens(hipStream_t st, const EncCtx &c);
 void launch_ac_runs(hipStream_t st, const EncCtx &c);
 void launch_gen_tables(hipStream_t st, DevEncTable *tables, int ntables);
@@ -182,6 +185,7 @@ void launch_pack(hipStream_t st, const EncCtx &c);
 // counts, has-symbol / ends-with-EOB flags) of the run's list slots -- in launch_tokens' place --; their bits -- in launch_pack's place
 void launch_nzlist(hipStream_t st, const EncCtx &c);
 void launch_list_stats(hipStream_t st, const EncCtx &c);
+void launch_list_refine(hipStream_t st, const EncCtx &c);   // tokens, flags and statistics of the run's refinement slots (EncCtx::ref_slots) -- in k_tokens' place
 void launch_list_pack(hipStream_t st, const EncCtx &c);
 // marks every work item "in no file, no bits" at the start of a run (a conditional stage of the scan search that does not run this time
 // must not leave the placement of an earlier run behind)

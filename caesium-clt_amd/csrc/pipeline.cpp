@@ -268,6 +268,7 @@ static int batch_run(csh_batch *b, csh_timing *t, bool requant_only) {
         t->n_images = uint32_t(b->nimg);
         t->n_search_extra = b->enc.search ? b->enc.n_gated_runs : 0u;
         t->n_fused_lists = b->enc.last_run_fused;
+        t->n_list_refine = b->enc.last_run_refine;
         for (const Item &it : b->items) if (it.image < 0) t->n_failed++;
         for (int i = 0; i < b->nimg; i++) { t->out_bytes += b->out.h_img_size[i]; t->pixels += uint64_t(b->imgs[i].width) * b->imgs[i].height; }
         t->in_bytes = b->dec.bits_pool.size();

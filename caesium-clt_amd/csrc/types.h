@@ -211,11 +211,13 @@ struct ScanWork {
     uint32_t out_off;      // offset of this scan's DHT marker inside the image's output file (device-computed)
     uint32_t hdr_bytes;    // DHT + SOS bytes in front of the entropy-coded data (device-computed)
     uint32_t no_room;      // the raw pool cannot hold this scan (device-computed): the packer skips it, the batch is re-run with a larger pool
-    uint32_t list;         // progressive AC scans: the NzList (component, point transform) the scan is coded from (k_aclist.hip); 0xFFFFFFFF otherwise
+    uint32_t list;         // progressive AC scans: the NzList (component, point transform Al) the scan is coded from (k_aclist.hip: first-pass scans and, unless CSH_REF_LIST=0, refinement scans); 0xFFFFFFFF otherwise
     uint32_t corr_base;    // refinement scans: the scan's first correction word in EncCtx::corr (one u64 per unit of a REFINEMENT scan only: 8 bytes for every unit of
                            // every candidate scan were 7.5 MB of a 1080p picture's 37 MB of pools); 0xFFFFFFFF otherwise
     uint32_t hist_row0;    // first histogram row of its first slot (slot j: hist_row0 + j * ntables)
-    uint32_t ls_base;      // where its slots stand in the list of list-coded slots (list != 0xFFFFFFFF) or of token-coded slots
+    uint32_t ls_base;      // where its slots stand in the list of list-coded slots (first-pass scans with a list) or of token-coded slots
+    uint32_t rs_base;      // refinement scans coded from their list (k_list_refine): where its slots stand in the list of such slots; 0xFFFFFFFF otherwise
+    uint32_t region;       // ... and the region of the token pool their tokens go to (one per image, component and stage)
 };
 
 // one workgroup of the token kernel (k_tokens): 256 consecutive units, [256 j, 256 j + 256)
@@ -271,11 +273,12 @@ struct SlotRec {
     uint32_t first_chunk;        // the work item's first slot
     uint32_t unit0, nun;         // first unit (index into the per-unit arrays) and number of units of the chunk
     uint32_t table_base;
-    uint16_t ntables, flags;     // flags: 1 progressive AC scan (EOB tokens), 2 refinement (correction words), 4 coded from its NzList (k_aclist.hip), not from tokens
+    uint16_t ntables, flags;     // flags: 1 progressive AC scan (EOB tokens), 2 refinement (correction words), 4 coded from its NzList (k_aclist.hip), not from tokens, 8 refinement whose tokens k_list_refine makes from its NzList
     uint32_t hist_row;           // first of the slot's ntables rows of 256 symbol counts (EncCtx::slot_hist)
     uint32_t word_base, unit_base, nunits_work;   // of the work item (k_ac_runs)
     uint8_t Ss, Se, Ah, Al; uint32_t corr0;           // corr0: the chunk's first correction word (refinement scans)
-    uint32_t nzlist, nzrec;      // list-coded slots: the NzList and the chunk's record in the per-chunk arrays (nz_chunk_off / nz_chunk_cnt)
+    uint32_t nzlist, nzrec;      // slots with a list (flags 4, 8): the NzList and the chunk's record in the per-chunk arrays (nz_chunk_off / nz_chunk_cnt)
+    uint32_t region;             // flags 8: the slot's region of the token pool
 };
 
 // mozjpeg's trellis quantiser (k_trellis.hip; CSH_PROFILE=mozjpeg): one work item per (image, component) -- the component's statistics

@@ -54,6 +54,41 @@ __device__ __forceinline__ static uint32_t lsum32(const LV<uint32_t> &x) {
     (void)lscan(x, s);
     return s;
 }
+// inclusive maximum scan over the lanes (all 64 lanes active)
+__device__ __forceinline__ static LV<uint32_t> lmaxscan(const LV<uint32_t> &x) {
+    LV<uint32_t> r;
+#ifdef CSH_EMUL
+    uint32_t m = 0;
+    for (int j = 0; j < 64; j++) { m = x.v[j] > m ? x.v[j] : m; r.v[j] = m; }
+#else
+    // the ladder of lscan with max for +: a lane a step does not reach takes `old` = 0, the identity
+    uint32_t v = x.v, t;
+    t = uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x111, 0xf, 0xf, false)); v = t > v ? t : v;
+    t = uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x112, 0xf, 0xf, false)); v = t > v ? t : v;
+    t = uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x114, 0xf, 0xf, false)); v = t > v ? t : v;
+    t = uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x118, 0xf, 0xf, false)); v = t > v ? t : v;
+    t = uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x142, 0xa, 0xf, false)); v = t > v ? t : v;
+    t = uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x143, 0xc, 0xf, false)); v = t > v ? t : v;
+    r.v = v;
+#endif
+    return r;
+}
+// "the last marked entry in front of me", four entries per lane (entry 4 l + q of the step is x[q][l]).  In: the key of a marked entry
+// (non-zero; the keys of marked entries never decrease along the list), 0 for the others.  Out: per entry the key of the last marked entry
+// in front of it, 0 if there is none.  carry: the last key of the steps before, and on return of this one too
+__device__ __forceinline__ static void lscan_last4(LV<uint32_t> (&x)[4], uint32_t &carry) {
+    LV<uint32_t> m;
+    LFOR(l) { const uint32_t a = x[0][l] > x[1][l] ? x[0][l] : x[1][l], b = x[2][l] > x[3][l] ? x[2][l] : x[3][l]; m[l] = a > b ? a : b; }
+    const LV<uint32_t> inc = lmaxscan(m);
+    const LV<uint32_t> ex = lprev(inc, 0u);
+    LFOR(l) {
+        uint32_t run = ex[l] > carry ? ex[l] : carry;
+        CSH_UNROLL
+        for (int q = 0; q < 4; q++) { const uint32_t t = x[q][l]; x[q][l] = run; run = t > run ? t : run; }
+    }
+    const uint32_t last = llast(inc);
+    carry = last > carry ? last : carry;
+}
 // per-wave state that lives across the phases of a phased kernel (gpu_rt.h CSH_PHASE_LOOP): plain registers on the device; the emulation re-enters
 // the kernel once per phase and wave-thread, so there it is a per-thread array indexed by the wave.  Declare it in front of CSH_PHASE_LOOP.
 #ifdef CSH_EMUL

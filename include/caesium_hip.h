@@ -135,6 +135,8 @@ typedef struct {
     uint32_t n_search_extra;      /* conditional stages of the scan search this run needed (0..3: luma at Al 3, the fourth and the fifth frequency split) */
     uint32_t n_fused_lists;       /* components whose level-0 coefficient list the forward-DCT kernels built in this run (0 with CSH_NZ_FUSED=0, in a re-quantisation run, and
                                      for components whose width is not a multiple of the MCU width: k_nzlist builds those from the tiles) */
+    uint32_t n_list_refine;       /* AC refinement scans (work items, the scan search's candidates included) this run coded from the coefficient lists (k_list_refine);
+                                     0 with CSH_REF_LIST=0 and for sequential output */
 } csh_timing;
 
 int csh_device_count(void);
