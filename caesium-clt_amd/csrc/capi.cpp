@@ -144,7 +144,7 @@ static int sniff(const uint8_t *d, size_t n);
 static int png_batch_compress(const CByteArray *inputs, size_t count, const CCSParameters *p, int device, CByteArray *outputs, CCSResult *results, bool to_webp = false) {
     int failed_total = 0;
     // png.force_zopfli (--zopfli): libcaesium hands the streams to zopfli; here the same coder runs CSP_DEEP_ITERS_ZOPFLI passes of its cost model
-    // over the chunks that take the min-cost-path parse (png_pipeline.cpp, png_parse.h)
+    // over the chunks that take the min-cost-path parse (png_run.cpp, png_parse.h)
     const uint64_t budget = uint64_t(96) << 30;
     for (size_t g0 = 0; g0 < count;) {
         uint64_t bytes = 0;

@@ -1,4 +1,4 @@
-// devmem.hpp -- device / pinned-host memory helpers shared by the batch objects (batch.hpp, png_pipeline.cpp)
+// devmem.hpp -- device / pinned-host memory helpers shared by the batch objects (batch.hpp, png_batch.hpp)
 #pragma once
 #include <algorithm>
 #include <atomic>

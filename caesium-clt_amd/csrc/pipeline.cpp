@@ -36,7 +36,7 @@ using namespace csh;
 // image-rs Lanczos3 taps of one axis (imageops::sample) -- host side, same libm calls as the oracle
 static float sincf_(float t) { float a = t * 3.14159265358979323846f; return t == 0.0f ? 1.0f : sinf(a) / a; }
 static float lanczos3f(float x) { return fabsf(x) < 3.0f ? sincf_(x) * sincf_(x / 3.0f) : 0.0f; }
-void csh_lanczos_axis(int in_size, int out_size, bool identity, std::vector<ResizeTap> &taps, std::vector<float> &weights) {   // also used by png_pipeline.cpp (resize_host.h)
+void csh_lanczos_axis(int in_size, int out_size, bool identity, std::vector<ResizeTap> &taps, std::vector<float> &weights) {   // also used by png_convert.cpp (resize_host.h)
     for (int o = 0; o < out_size; o++) {
         ResizeTap t;
         t.woff = uint32_t(weights.size());

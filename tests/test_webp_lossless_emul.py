@@ -124,3 +124,21 @@ def test_emul_png_to_lossless_webp(api):
         as_png = api.compress_in_memory(cases[name], params(png_optimize=True, width=40))
         got, want = Image.open(io.BytesIO(small)), Image.open(io.BytesIO(as_png))
         assert got.size == want.size and got.size[0] == 40 and np.array_equal(np.asarray(got.convert("RGBA")), np.asarray(want.convert("RGBA"))), name
+
+
+def test_emul_small_transparent_png_resized_to_lossless_webp(api):
+    """19 x 13 grey + alpha and RGBA pictures (partial blocks everywhere, a one-row last Adam7 pass in the interlaced one) to lossless WebP with a size: the
+    PNG row's own Lanczos passes.  The file is the oracle's VP8L statement of its pixels, byte for byte, and the pixels are those of the PNG -> PNG resize."""
+    from test_png_webp_emul import make_png
+    from _util import adam7_png
+    rng = np.random.default_rng(19)
+    la = make_png(19, 13, 8, 4, rng.integers(0, 256, (13, 19, 2), dtype=np.uint8).tobytes())
+    rgba = make_png(19, 13, 8, 6, rng.integers(0, 256, (13, 19, 4), dtype=np.uint8).tobytes())
+    for name, src in (("la", la), ("rgba", rgba), ("rgba_adam7", adam7_png(rgba))):
+        for size in ({"width": 11}, {"width": 30, "height": 7}):
+            out = api.convert_in_memory(src, params(webp_lossless=True, **size), 3)
+            as_png = api.compress_in_memory(src, params(png_optimize=True, **size))
+            got, want = Image.open(io.BytesIO(out)), Image.open(io.BytesIO(as_png))
+            assert got.mode == "RGBA" and got.size == want.size and got.size[0] == size["width"], (name, size)
+            assert np.array_equal(np.asarray(got), np.asarray(want.convert("RGBA"))), (name, size)
+            assert out == oracle_vp8l(out), (name, size)

@@ -45,3 +45,7 @@ def test_device_writes_the_oracles_bytes(api):
 
 def test_png_to_lossless_webp(api):
     E.test_emul_png_to_lossless_webp(api)
+
+
+def test_small_transparent_png_resized_to_lossless_webp(api):
+    E.test_emul_small_transparent_png_resized_to_lossless_webp(api)
