@@ -129,6 +129,11 @@ struct EncodePlan {
     std::vector<NzChunk> nzchunks_fused;
     uint32_t n_fused = 0;                 // components whose list the transform builds (csh_timing.n_fused_lists of a run that does)
     uint32_t last_run_fused = 0;          // ... of the last run
+    // of those, the components whose quantised AC levels no coding kernel reads from the tiles (PlaneWork::ac_lists): a run whose transform builds the lists does not
+    // store them there (csh_timing.n_ac_in_lists), and csh_batch_read_coefs writes them back from the lists on demand
+    uint32_t n_ac_lists = 0;
+    uint32_t last_run_ac_lists = 0;       // ... of the last run
+    std::vector<uint8_t> nzset_ac_lists;  // per set: such a component
     std::vector<uint32_t> nz_est, nz_worst; // per list: estimated / largest possible number of entries
     uint32_t nz_nrec = 0;                 // per-(list, chunk) records
     uint64_t nz_cap = 0;                  // pool capacity: the sum of the regions
@@ -302,6 +307,7 @@ struct PlanSwitches {
     bool fused_420 = true;      // CSH_NO_FUSED_420 unset
     bool nz_fused = true;       // CSH_NZ_FUSED != "0": the forward-DCT kernels build the level-0 coefficient lists
     bool ref_list = true;       // CSH_REF_LIST != "0": the AC refinement scans are coded from the coefficient lists (k_list_refine), not from the tiles (k_tokens' kind-0 chunks)
+    bool ac_tiles = false;      // CSH_AC_TILES == "1": every component's AC levels are stored to its tiles, as before they lived in the lists
     static PlanSwitches read();
 };
 

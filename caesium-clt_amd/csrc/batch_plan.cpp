@@ -236,6 +236,7 @@ PlanSwitches PlanSwitches::read() {
     s.nz_once = !is("CSH_NZ_ONCE", "0");
     s.tr_sort = !is("CSH_TR_SORT", "0");
     s.nz_fused = !is("CSH_NZ_FUSED", "0");
+    s.ac_tiles = is("CSH_AC_TILES", "1");
     s.ref_list = is("CSH_REF_LIST", "1") || (s.ref_list && !is("CSH_REF_LIST", "0"));   // "1" / "0" name the path, anything else leaves the default
     const char *pp = getenv("CSH_PROG_PAR");
     s.prog_par = pp && !strcmp(pp, "0") ? 0 : (pp && !strcmp(pp, "1") ? 1 : -1);
@@ -787,7 +788,7 @@ bool BatchPlanner::progressive_plan(const Item &it, const ImgDesc &im, int img_i
 // pixel work + planes
 void BatchPlanner::plane_work(ImgDesc &im, const JpegInfo &in, const JpegInfo &o, int img_index, bool resized) {
     for (int c = 0; c < in.ncomp; c++) {
-        PlaneWork w; w.image = img_index; w.comp = c; w.nzset = 0xFFFFFFFFu;   // (finish_descriptors names the set: the lists are planned behind the pixel work)
+        PlaneWork w; w.image = img_index; w.comp = c; w.nzset = 0xFFFFFFFFu; w.ac_lists = 0u;   // (finish_descriptors names the set: the lists are planned behind the pixel work)
         w.up = resized ? up_desc(1, 1, 0) : up_desc(in.hmax / in.comp[c].h, in.vmax / in.comp[c].v, in.comp[c].comp_w);
         w.dn = dn_kind(o.hmax / o.comp[c].h, o.vmax / o.comp[c].v);
         // the layouts k_resample_plane takes keep its mode numbers (in: 0 full, 1 h2v2, 2 h2v1 by the up factors); every other one is CSH_MODE_ANY
@@ -1084,14 +1085,27 @@ void BatchPlanner::finish_descriptors() {
         b->enc.nzchunks_fused = b->enc.nzchunks;
         const bool allowed = sw.nz_fused && !b->lossless && !b->webp && !b->rgb_out && !(b->tr.trellis && progressive && !b->tr.nz_once);
         std::vector<uint8_t> fused(b->enc.nzsets.size(), 0);
+        // ... and of which of those does nothing read the quantised AC levels from the tiles any more (PlaneWork::ac_lists)?  Progressive output whose refinement scans
+        // are coded from the lists too (no kind-0 chunk of k_tokens: no TokPlan of the component) and, under the trellis quantiser, whose trellis writes its levels
+        // into the list (t_sort and nz_once).  Each of the fallback switches keeps the tiles whole by itself, in every profile; so does CSH_AC_TILES=1
+        const bool lists_only = progressive && !sw.ac_tiles && sw.ref_list && sw.nz_once && sw.tr_sort && (!b->tr.trellis || (b->tr.t_sort && b->tr.nz_once));
+        std::vector<uint8_t> planned(b->enc.nzsets.size(), 0);   // some TokPlan reads the component's tiles
+        for (size_t i = 0; i < b->enc.plans.size(); i++) {
+            const size_t at = size_t(b->enc.plan_image[i]) * CSH_MAX_COMPS + size_t(b->enc.plan_comp[i]);
+            if (at < b->enc.nzset_of.size() && b->enc.nzset_of[at] >= 0) planned[size_t(b->enc.nzset_of[at])] = 1;
+        }
+        b->enc.nzset_ac_lists.assign(b->enc.nzsets.size(), 0);
         for (PlaneWork &w : b->pix.pwork) {
+            w.ac_lists = 0u;
             const size_t at = size_t(w.image) * CSH_MAX_COMPS + size_t(w.comp);
             const int si = allowed && at < b->enc.nzset_of.size() ? b->enc.nzset_of[at] : -1;
             if (si < 0) continue;
             const NzSet &S = b->enc.nzsets[size_t(si)];
             if (S.real_bw != S.bw || S.list[0] == 0xFFFFFFFFu) continue;
             w.nzset = uint32_t(si); fused[size_t(si)] = 1; b->enc.n_fused++;
+            if (lists_only && !planned[size_t(si)]) { w.ac_lists = 1u; b->enc.nzset_ac_lists[size_t(si)] = 1; b->enc.n_ac_lists++; }
         }
+        for (TrellisWork &tw : b->tr.twork) tw.ac_lists = (tw.nzset != 0xFFFFFFFFu && b->enc.nzset_ac_lists[tw.nzset]) ? 1u : 0u;
         for (NzChunk &ch : b->enc.nzchunks_fused) if (fused[ch.set]) ch.levels &= ~1u;
         auto flags = [&](Stage &sg) {
             for (int f = 0; f < 2; f++) {

@@ -212,6 +212,10 @@ struct Run {
             nzf.blk_cnt = (b->tr.trellis && b->tr.t_sort) ? b->tr.d_tblk_cnt.p : nullptr;
             nzf.blk_off = (nzf.blk_cnt && b->tr.nz_once) ? b->tr.d_tblk_off.p : nullptr;
         }
+        // (CSH_DEBUG bit 32768, for the tests: the output tiles start the run as garbage.  A component whose AC levels live in the lists -- PlaneWork::ac_lists -- carries
+        // it in octets 1..7 through the whole run: a kernel that still read them there would change the files)
+        if (nw && getenv("CSH_DEBUG") && (uint32_t(atoi(getenv("CSH_DEBUG"))) & 32768u))
+            CSH_CHECK(hipMemsetAsync(b->d_coef.p + size_t(b->ntiles_in) * CSH_TILE_I16, 0x5A, size_t(b->ntiles - b->ntiles_in) * CSH_TILE_I16 * sizeof(int16_t), st));
         launch_xform_direct(st, b->d_imgs.p, b->pix.d_pwork.p, nw, b->max_tiles, b->d_quants.p, b->d_coef.p, b->d_coef.p, rawp, b->ntiles_in, b->tr.dering, nzf);
         MARK(KS_XFORM_DIRECT);
         launch_resample_plane(st, b->d_imgs.p, b->pix.d_pwork.p, nw, b->pix.max_quads, b->pix.d_planes.p, b->pix.d_oplanes.p);
@@ -258,6 +262,7 @@ struct Run {
             tc.nz_pool = b->enc.d_nz_pool.p; tc.nzlists = b->enc.d_nzlists.p; tc.nzsets = b->enc.d_nzsets.p; tc.nz_chunk_off = b->enc.d_nz_chunk_off.p; tc.nz_chunk_cnt = b->enc.d_nz_chunk_cnt.p;
             tc.blk_off = b->tr.d_tblk_off.p;
         }
+        tc.ac_lists = fused ? 1u : 0u;   // (only a run whose transform built the lists left the flagged components' AC levels out of the tiles)
         tc.debug = getenv("CSH_TR_DEBUG") ? uint32_t(atoi(getenv("CSH_TR_DEBUG"))) : 0u;
     }
 
@@ -437,7 +442,7 @@ struct Run {
 
 int run_once(csh_batch *b, csh_timing *t, bool requant_only) {
     Run r(b, t);
-    b->enc.last_run_fused = 0; b->enc.last_run_refine = 0;
+    b->enc.last_run_fused = 0; b->enc.last_run_refine = 0; b->enc.last_run_ac_lists = 0;
     if (r.pools() || r.marks.start()) return -1;
     // a re-run at another quality (size targeting): from the retained DCT -- unless the batch derings: the overshoot mozjpeg's deringing allows
     // depends on the DC quantiser (jcdctmgr.c preprocess_deringing), so the forward DCT's input changes with the table and the re-run starts
@@ -454,6 +459,7 @@ int run_once(csh_batch *b, csh_timing *t, bool requant_only) {
     }
     if (r.encode_begin()) return -1;
     b->enc.last_run_fused = r.fused ? b->enc.n_fused : 0u;
+    b->enc.last_run_ac_lists = r.fused ? b->enc.n_ac_lists : 0u;
     if (b->tr.trellis ? r.trellis() : r.marks.skip_to(KS_NZLIST)) return -1;
     r.fill_asm_ctx();
     if (r.stage(b->enc.stage[0], true, false)) return -1;

@@ -246,6 +246,43 @@ __global__ void __launch_bounds__(64) k_nzfilter(EncCtx c) {
     }
 }
 
+// ---- the way back, for the debug tap (csh_batch_read_coefs): a component whose AC levels the run kept in its level-0 list alone (PlaneWork::ac_lists) gets them
+// written into its tiles again.  One workgroup per 256-block chunk of the list: every block's AC is zeroed -- octets 1..7, and coefficients 1..7 of octet 0, which
+// hold the scalar quantiser's levels whatever the trellis made of them; the DC stays --, then the chunk's entries go to their places, with their signs.  An entry of
+// magnitude 0 (a coefficient the trellis dropped, in a list k_nzfilter has not compacted) writes the zero that is there already; END entries and padding write
+// nothing.  The list is only read, and the tile's AC is written from nothing but the list: calling it again changes nothing, and no later run reads what it wrote
+__global__ void __launch_bounds__(256) k_nz_to_tiles(const NzSet *nzsets, const NzList *nzlists, const uint32_t *nz_pool, const uint32_t *nz_chunk_off, const uint32_t *nz_chunk_cnt, uint32_t set,
+                                                      int16_t *coef) {
+    const NzSet S = nzsets[set];
+    const NzList L0 = nzlists[S.list[0]];
+    const uint32_t j = blockIdx.x, u0 = j * 256u;
+    CSH_PHASE_LOOP(2) {
+        if (phase == 0) {
+            const uint32_t u = u0 + threadIdx.x;
+            if (u >= S.nunits) continue;
+            const int by = int(u) / S.real_bw, bx = int(u) - by * S.real_bw;
+            int16_t *blk = coef + coef_index(S.tile_base, by * S.bw + bx, 0);
+            uint4 z; z.x = z.y = z.z = z.w = 0u;
+            z.x = uint32_t(uint16_t(blk[0]));
+            CSH_UNROLL
+            for (int o = 0; o < 8; o++) { *reinterpret_cast<uint4 *>(blk + CSH_OCT_STRIDE * o) = z; z.x = 0u; }
+            continue;
+        }
+        const uint32_t n = nz_chunk_cnt[L0.chunk0 + j];
+        const uint32_t *src = nz_pool + L0.base + nz_chunk_off[L0.chunk0 + j];
+        for (uint32_t i = threadIdx.x; i < n; i += 256u) {
+            const uint32_t e = src[i], k = e & 127u, u = u0 + ((e >> 23) & 255u);
+            if (k == 0u || k >= CSH_NZ_END || u >= S.nunits) continue;
+            const int by = int(u) / S.real_bw, bx = int(u) - by * S.real_bw, m = int((e >> 8) & 0x7FFFu);
+            coef[coef_index(S.tile_base, by * S.bw + bx, int(k))] = int16_t((e & 128u) ? -m : m);
+        }
+    }
+}
+void launch_nz_to_tiles(hipStream_t st, const NzSet *nzsets, const NzList *nzlists, const uint32_t *nz_pool, const uint32_t *nz_chunk_off, const uint32_t *nz_chunk_cnt, uint32_t set,
+                        uint32_t nchunks, int16_t *coef) {
+    if (nchunks) CSH_LAUNCH_PHASED(k_nz_to_tiles, 2, dim3(nchunks), dim3(256), st, nzsets, nzlists, nz_pool, nz_chunk_off, nz_chunk_cnt, set, coef);
+}
+
 // ------------------------------------------------------------------------------------------------ the events of a first-pass scan
 // What entry e means in scan (Ss, Se), given the entry p in front of it (the END of the block before: CSH_NZ_END):
 //   coded   Ss <= k <= Se: symbol (run & 15) << 4 | size, run >> 4 ZRLs in front of it, `size` value bits

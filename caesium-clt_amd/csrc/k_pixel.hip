@@ -183,23 +183,25 @@ __device__ __forceinline__ static uint32_t quant_one(const int x[64], const DevQ
     return float_bits(__builtin_fmaf(float(x[kZ2N[K]]), q.rcp[K], 12582912.0f));   // low half = the level
 }
 // lv: the block's levels as they are stored, octet by octet -- what the list builder below (nzf_*) works from
+// dc_only (workgroup-uniform; PlaneWork::ac_lists): the levels of octets 1..7 go to the list builder alone -- no coding kernel reads them from the tile.  Octet 0 is
+// stored whole, as ever: it carries the DC, which every DC reader takes from the tile
 template <int J>
-__device__ __forceinline__ static void quant_store_octet(const int x[64], const DevQuant &q, int16_t *__restrict__ blk /* of octet J & ~3 */, uint4 &v) {
+__device__ __forceinline__ static void quant_store_octet(const int x[64], const DevQuant &q, int16_t *__restrict__ blk /* of octet J & ~3 */, uint4 &v, bool dc_only) {
     v.x = pack_halves(quant_one<8 * J + 0>(x, q), quant_one<8 * J + 1>(x, q));
     v.y = pack_halves(quant_one<8 * J + 2>(x, q), quant_one<8 * J + 3>(x, q));
     v.z = pack_halves(quant_one<8 * J + 4>(x, q), quant_one<8 * J + 5>(x, q));
     v.w = pack_halves(quant_one<8 * J + 6>(x, q), quant_one<8 * J + 7>(x, q));
-    nt_store16(blk + CSH_OCT_STRIDE * (J & 3), v);
+    if (J == 0 || !dc_only) nt_store16(blk + CSH_OCT_STRIDE * (J & 3), v);
 }
 template <int... J>
-__device__ __forceinline__ static void quant_store_all(const int x[64], const DevQuant &q, int16_t *__restrict__ blk, uint4 lv[8], std::integer_sequence<int, J...>) {
+__device__ __forceinline__ static void quant_store_all(const int x[64], const DevQuant &q, int16_t *__restrict__ blk, uint4 lv[8], bool dc_only, std::integer_sequence<int, J...>) {
     // The eight stores of a block are 1 KiB apart and a store's immediate offset ends at 4 KiB: octets 4..7 get a base of their own, made HERE.  (Left to itself the
     // compiler makes four more 64-bit addresses at the top of the kernel and carries them through the whole transform: eight registers the levels' stay in lv needs.)
     int16_t *hi = blk + 4 * CSH_OCT_STRIDE;
 #ifndef CSH_EMUL
     asm volatile("" : "+v"(hi));
 #endif
-    ((quant_store_octet<J>(x, q, J < 4 ? blk : hi, lv[J]), CSH_SCHED_FENCE()), ...);
+    ((quant_store_octet<J>(x, q, J < 4 ? blk : hi, lv[J], dc_only), CSH_SCHED_FENCE()), ...);
 }
 template <int J>
 __device__ __forceinline__ static void raw_store_octet(const int x[64], int16_t *__restrict__ raw) {
@@ -418,7 +420,7 @@ __device__ __forceinline__ static void dering_block_pk(uint32_t pr[8][4], int dc
 }
 // where block b of a component goes: its tile in the coefficient pool and, if the unquantised DCT is retained (dct_raw not null), its place there.  The two addresses
 // are made where they are used, behind the transform, from the block number: made at the top of the kernel they are four registers carried through all of it
-struct BlkOut { int16_t *coef_out; uint32_t tile_base; int b; int16_t *dct_raw; uint32_t raw_tile_base; };
+struct BlkOut { int16_t *coef_out; uint32_t tile_base; int b; int16_t *dct_raw; uint32_t raw_tile_base; bool dc_only; /* quant_store_octet */ };
 // packed rows -> [deringing] -> 2-D FDCT -> [retained DCT] -> quantise -> store
 template <bool DERING, bool CENTRED>
 __device__ __forceinline__ static void fdct_quant_store_pk(uint32_t pr[8][4], const DevQuant &q, const BlkOut &o, uint4 lv[8], CSH_DERING_LDS) {
@@ -445,7 +447,7 @@ __device__ __forceinline__ static void fdct_quant_store_pk(uint32_t pr[8][4], co
     if (o.dct_raw) {   // size-targeting keeps the unquantised DCT so later tries only re-quantise; the trellis quantiser works from it
         if (CSH_RAW_VIA_LDS) raw_put_all(x, dr_col, int(threadIdx.x), Oct()); else raw_store_all(x, o.dct_raw + raw_index(o.raw_tile_base, b), Oct());
     }
-    quant_store_all(x, q, o.coef_out + coef_index(o.tile_base, b, 0), lv, Oct());
+    quant_store_all(x, q, o.coef_out + coef_index(o.tile_base, b, 0), lv, o.dc_only, Oct());
 }
 // centred samples in registers (natural order) -> the packed rows
 __device__ __forceinline__ static void pack_rows(const int x[64], uint32_t pr[8][4]) {
@@ -465,7 +467,7 @@ __device__ __forceinline__ static void fdct_quant_store(int x[64], const DevQuan
 template <bool DERING, bool CENTRED = false>
 __device__ __forceinline__ static void fdct_quant_store(int x[64], const DevQuant &q, int16_t *__restrict__ blk, int16_t *__restrict__ raw, CSH_DERING_LDS) {
     uint4 lv[8];
-    fdct_quant_store<DERING, CENTRED>(x, q, BlkOut{blk, 0u, 0, raw, 0u}, lv, dr_col);
+    fdct_quant_store<DERING, CENTRED>(x, q, BlkOut{blk, 0u, 0, raw, 0u, false}, lv, dr_col);
 }
 
 // re-quantise a retained DCT block with another table (k_requant)
@@ -479,7 +481,7 @@ __device__ __forceinline__ static void requant_block(const int16_t *__restrict__
     int x[64];
     (raw_to_nat<J>(x, v[J], Oct()), ...);
     uint4 lv[8];
-    quant_store_all(x, q, blk, lv, Oct());
+    quant_store_all(x, q, blk, lv, false, Oct());
 }
 
 __device__ __forceinline__ static void store_zero_block(int16_t *__restrict__ blk) {
@@ -546,6 +548,9 @@ __device__ __forceinline__ static void nzf_walk(const uint4 lv[8], uint32_t blk,
     ((nzf_octet<J>(lv[J], kb, dst, o), CSH_SCHED_FENCE()), ...);
     dst[o] = CSH_NZ_END | kb;
 }
+// does this launch leave the AC levels of the work item's blocks to the list alone?  (workgroup-uniform.  Only where it builds the list: every real block of such a
+// component lies in a workgroup that builds a chunk -- real_bw == bw, so the blocks behind the last real one are dummy rows, which store_zero_block writes whole)
+__device__ __forceinline__ static bool nzf_dc_only(const NzFuse &f, const PlaneWork &w) { return f.nz_pool != nullptr && w.nzset != 0xFFFFFFFFu && w.ac_lists != 0u; }
 // does this workgroup build a chunk?  (workgroup-uniform)
 __device__ __forceinline__ static bool nzf_begin(const NzFuse &f, const PlaneWork &w, NzSet &S) {
     if (!f.nz_pool || w.nzset == 0xFFFFFFFFu) return false;
@@ -664,7 +669,7 @@ __global__ void __launch_bounds__(256) k_xform_direct(const ImgDesc *__restrict_
         load_idct<true>(coef_in + coef_index(gi.tile_base, by * gi.bw + bx, 0), quant[CSH_UNIFORM(im.qt_in[w.comp])], x);
         int vc = gi.comp_w - bx * 8, vr = gi.comp_h - by * 8;
         if (vc < 8 || vr < 8) replicate_edges(x, vc, vr);
-        fdct_quant_store<DERING, true>(x, quant[CSH_UNIFORM(im.qt_out[w.comp])], BlkOut{coef_out, go.tile_base, b, dct_raw, go.tile_base - raw_tile0}, lv, s_dr);
+        fdct_quant_store<DERING, true>(x, quant[CSH_UNIFORM(im.qt_out[w.comp])], BlkOut{coef_out, go.tile_base, b, dct_raw, go.tile_base - raw_tile0, nzf_dc_only(nzf, w)}, lv, s_dr);
         has_raw = dct_raw != nullptr;
     } while (0);
     if (dct_raw) raw_copy_out(dct_raw + raw_index(go.tile_base - raw_tile0, tile * 64), has_raw, s_dr, int(threadIdx.x));
@@ -983,7 +988,7 @@ __global__ void __launch_bounds__(256) k_plane_fdct(const ImgDesc *__restrict__ 
         const uint2 v = *reinterpret_cast<const uint2 *>(p + size_t(r) * pitch);
         pr[r][0] = bytes_to_halves<0, 1>(v.x); pr[r][2] = bytes_to_halves<2, 3>(v.x); pr[r][1] = bytes_to_halves<3, 2>(v.y); pr[r][3] = bytes_to_halves<1, 0>(v.y);
     }
-    fdct_quant_store_pk<DERING, false>(pr, quant[CSH_UNIFORM(im.qt_out[w.comp])], BlkOut{coef_out, go.tile_base, b, dct_raw, go.tile_base - raw_tile0}, lv, s_dr);
+    fdct_quant_store_pk<DERING, false>(pr, quant[CSH_UNIFORM(im.qt_out[w.comp])], BlkOut{coef_out, go.tile_base, b, dct_raw, go.tile_base - raw_tile0, nzf_dc_only(nzf, w)}, lv, s_dr);
     has_raw = dct_raw != nullptr;
     } while (0);
     if (dct_raw) raw_copy_out(dct_raw + raw_index(go.tile_base - raw_tile0, tile * 64), has_raw, s_dr, int(threadIdx.x));
@@ -1122,7 +1127,7 @@ __global__ void __launch_bounds__(256) k_resample_fdct_420(const ImgDesc *__rest
                 for (int cc = 0; cc < 4; cc++) pr[r][cc] = pr[r - 1][cc];
             }
     }
-    fdct_quant_store_pk<DERING, false>(pr, quant[CSH_UNIFORM(im.qt_out[w.comp])], BlkOut{coef_out, go.tile_base, b, dct_raw, go.tile_base - raw_tile0}, lv, s_dr);
+    fdct_quant_store_pk<DERING, false>(pr, quant[CSH_UNIFORM(im.qt_out[w.comp])], BlkOut{coef_out, go.tile_base, b, dct_raw, go.tile_base - raw_tile0, nzf_dc_only(nzf, w)}, lv, s_dr);
     has_raw = dct_raw != nullptr;
     } while (0);
     if (dct_raw) raw_copy_out(dct_raw + raw_index(go.tile_base - raw_tile0, tile * 64), has_raw, s_dr, int(threadIdx.x));

@@ -283,8 +283,8 @@ __device__ __forceinline__ static void trellis_block(const TrellisCtx &c, uint32
     }
 
     if (c.debug & 4u) return;
-    // ---- the block.  It holds the scalar quantiser's output (the pixel kernels wrote it: zeros wherever the list has no entry, the scalar DC,
-    // which k_trellis_dc replaces): only the list's positions change -- the level chosen on the path back from the last coefficient, zero off
+    // ---- the block.  Where the tile is written (to_tile below) it holds the scalar quantiser's output (the pixel kernels wrote it: zeros wherever the list has no
+    // entry, the scalar DC, which k_trellis_dc replaces): only the list's positions change -- the level chosen on the path back from the last coefficient, zero off
     // the path.  (Writing the block anew -- zeros, DC, levels -- was 128 bytes a block and, with the blocks in order of list length, most of
     // what that order cost: scattered 16-byte stores.)
     uint64_t kept = 0;   // entries on the path
@@ -296,7 +296,11 @@ __device__ __forceinline__ static void trellis_block(const TrellisCtx &c, uint32
             e = int(Pe & 63u) - 1;
         }
     }
-    int16_t *dst = c.coef + coef_index(g.tile_base, b, 0);
+    // ... unless the component's AC levels live in the list alone (TrellisWork::ac_lists, in a run whose transform left them out of the tile as well): no coding kernel
+    // reads them from the tile, and a lone 2-byte store per changed coefficient, blocks in order of list length, was a partial-sector write each.
+    // Without to_tile octets 1..7 of the block were never written: the chosen level lives in ent[] below alone, kept-at-the-scalar-level entries included
+    const bool to_tile = !(c.ac_lists && w.ac_lists);
+    int16_t *dst = to_tile ? c.coef + coef_index(g.tile_base, b, 0) : nullptr;
     // the block's entries in the statistics scan's level-0 list (the same coefficients in the same order: both are "scalar level not zero", in
     // zig-zag order): they take the chosen levels, so that the coding stages' lists are filtered from this list (k_nzfilter) and the
     // coefficient tiles are not swept a second time
@@ -327,7 +331,7 @@ __device__ __forceinline__ static void trellis_block(const TrellisCtx &c, uint32
                 uint32_t Pe;
                 if (e < CSH_TR_CAP) Pe = L.P[e][tid]; else Pe = CSH_SPILL_LD(sp + ((e - CSH_TR_CAP) * 3u + 2u) * CSH_TR_WGU);
                 const int pos = int((Pe >> 15) & 63u), level = ((kept >> e) & 1ull) ? int((Pe >> 21) & 1023u) : 0;
-                if (!(((kept >> e) & 1ull) && (Pe & 0x4000u))) dst[coef_off(pos)] = int16_t((Pe >> 31) ? -level : level);   // kept at the scalar level: the tile holds it
+                if (to_tile && !(((kept >> e) & 1ull) && (Pe & 0x4000u))) dst[coef_off(pos)] = int16_t((Pe >> 31) ? -level : level);   // kept at the scalar level: the tile holds it
                 ent[i] = uint32_t(pos) | ((Pe >> 31) ? 128u : 0u) | (uint32_t(level) << 8) | ((u & 255u) << 23);
             }
         }

@@ -152,7 +152,8 @@ struct EncCtx {  // device pointers + sizes every entropy kernel needs
     uint64_t raw_words;        // capacity of raw in u32 words
     uint32_t *status;          // per image
     uint32_t *overflow;        // [4]: [1] = the token pool was too small
-    uint32_t debug;            // CSH_DEBUG: performance experiments (parts of k_tokens switched off; output is then garbage)
+    uint32_t debug;            // CSH_DEBUG: performance experiments (parts of k_tokens switched off; output is then garbage).  Bits 1 .. 16384 are k_tokens' (k_entropy.hip);
+                               // bit 32768 is taken: Run::pixels() reads it from the same variable (the tests' poison of the output tiles, batch_run.cpp) -- no kernel may give it a meaning
     uint32_t stats_only;       // the trellis stage's statistics scans: histograms, flags and EOB runs only -- no token is written
     const uint8_t *work_active;// null: every work item of the run is coded; else per work item 1 = coded, 0 = skipped (conditional stages of the scan search)
     // the compacted coefficient lists and the slots coded from them (k_aclist.hip, types.h NzList)
@@ -187,6 +188,10 @@ void launch_nzlist(hipStream_t st, const EncCtx &c);
 void launch_list_stats(hipStream_t st, const EncCtx &c);
 void launch_list_refine(hipStream_t st, const EncCtx &c);   // tokens, flags and statistics of the run's refinement slots (EncCtx::ref_slots) -- in k_tokens' place
 void launch_list_pack(hipStream_t st, const EncCtx &c);
+// the debug tap's way back (csh_batch_read_coefs): the AC coefficients of component `set`, whose levels the last run kept in its level-0 list alone
+// (PlaneWork::ac_lists), written into its tiles again -- every block's AC zeroed, then the list's entries scattered; the DC stays.  Off the hot path
+void launch_nz_to_tiles(hipStream_t st, const NzSet *nzsets, const NzList *nzlists, const uint32_t *nz_pool, const uint32_t *nz_chunk_off, const uint32_t *nz_chunk_cnt,
+                        uint32_t set, uint32_t nchunks, int16_t *coef);
 // marks every work item "in no file, no bits" at the start of a run (a conditional stage of the scan search that does not run this time
 // must not leave the placement of an earlier run behind)
 void launch_reset_works(hipStream_t st, ScanWork *work, int nwork);
@@ -229,6 +234,7 @@ struct TrellisCtx {
     const NzSet *nzsets;
     const uint32_t *nz_chunk_off, *nz_chunk_cnt;
     const uint16_t *blk_off;   // EncCtx::nz_blk_off
+    uint32_t ac_lists;         // this run's forward-DCT kernels built the lists and left the AC levels of the flagged components (TrellisWork::ac_lists) out of the tiles: so does k_trellis_ac
 };
 void launch_trellis_sort(hipStream_t st, const TrellisCtx &c);   // fills TrellisCtx::perm from ::blk_cnt
 void launch_trellis_ac(hipStream_t st, const TrellisCtx &c);

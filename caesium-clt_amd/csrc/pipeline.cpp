@@ -269,6 +269,7 @@ static int batch_run(csh_batch *b, csh_timing *t, bool requant_only) {
         t->n_search_extra = b->enc.search ? b->enc.n_gated_runs : 0u;
         t->n_fused_lists = b->enc.last_run_fused;
         t->n_list_refine = b->enc.last_run_refine;
+        t->n_ac_in_lists = b->enc.last_run_ac_lists;
         for (const Item &it : b->items) if (it.image < 0) t->n_failed++;
         for (int i = 0; i < b->nimg; i++) { t->out_bytes += b->out.h_img_size[i]; t->pixels += uint64_t(b->imgs[i].width) * b->imgs[i].height; }
         t->in_bytes = b->dec.bits_pool.size();
@@ -355,6 +356,15 @@ extern "C" int csh_batch_read_coefs(csh_batch *b, size_t image, int comp, int wh
     if (csh_batch_geometry(b, image, comp, which, &bw, &bh, &rbw, &rbh)) return -1;
     const ImgDesc &im = b->imgs[b->items[image].image];
     const CompGeom &g = which ? im.out[comp] : im.in[comp];
+    {   // a component whose AC levels the last run kept in its level-0 list alone: they are written into its tiles here, on the batch's stream, before the copy
+        const size_t at = size_t(b->items[image].image) * CSH_MAX_COMPS + size_t(comp);
+        const int si = (which && b->enc.last_run_ac_lists && at < b->enc.nzset_of.size()) ? b->enc.nzset_of[at] : -1;
+        if (si >= 0 && size_t(si) < b->enc.nzset_ac_lists.size() && b->enc.nzset_ac_lists[size_t(si)]) {
+            if (hipSetDevice(b->device) != hipSuccess) { csh_set_error("hipSetDevice failed"); return -1; }
+            launch_nz_to_tiles(b->stream, b->enc.d_nzsets.p, b->enc.d_nzlists.p, b->enc.d_nz_pool.p, b->enc.d_nz_chunk_off.p, b->enc.d_nz_chunk_cnt.p, uint32_t(si),
+                               (b->enc.nzsets[size_t(si)].nunits + 255u) / 256u, b->d_coef.p);
+        }
+    }
     std::vector<int16_t> tiles(size_t(g.ntiles) * CSH_TILE_I16);
     if (csh_copy_wait(tiles.data(), b->d_coef.p + size_t(g.tile_base) * CSH_TILE_I16, tiles.size() * 2, hipMemcpyDeviceToHost, b->stream) != hipSuccess) { csh_set_error("D2H failed"); return -1; }
     for (int blk = 0; blk < bw * bh; blk++)

@@ -170,6 +170,8 @@ struct PlaneWork {
     UpDesc up;     // the decoded plane (resize path: the full-resolution plane of the resized image, CSH_UP_COPY)
     int dn;        // CSH_DN_*: the encoder's downsampling
     uint32_t nzset; // the component's NzSet when the forward-DCT kernel builds its level-0 list (k_pixel.hip nzf_*: real_bw == bw, so a workgroup's 256 blocks are a list chunk); 0xFFFFFFFF: not here
+    uint32_t ac_lists; // 1: nothing reads the component's quantised AC levels from its tiles -- every coding kernel takes them from the lists (batch_plan.cpp finish_descriptors) --, so a
+                       // launch that builds the list stores octet 0 of a block only (the DC and, dead, coefficients 1..7); csh_batch_read_coefs rebuilds the tile on demand (k_nz_to_tiles)
 };
 
 // resize path work item (k_resize.hip): one image
@@ -290,7 +292,7 @@ struct TrellisWork {
     uint32_t nunits;         // real blocks of the component
     uint32_t unit_base;      // first entry of the component in the per-block side arrays (lambda, DC back-pointers)
     uint32_t nzset;          // the component's NzSet (its level-0 list takes the chosen levels: TrellisCtx::nz_pool), 0xFFFFFFFF: none
-    uint32_t pad[1];
+    uint32_t ac_lists;       // 1: the component's AC levels live in that list alone (PlaneWork::ac_lists): in a run that says so (TrellisCtx::ac_lists) k_trellis_ac does not store them to the tile
 };
 // what one grab of k_trellis_ac's queue hands a workgroup: chunks j .. j + n - 1 of a work item (one staging of its tables for all n)
 struct TrellisRun { uint32_t work, j, n; };

@@ -137,6 +137,9 @@ typedef struct {
                                      for components whose width is not a multiple of the MCU width: k_nzlist builds those from the tiles) */
     uint32_t n_list_refine;       /* AC refinement scans (work items, the scan search's candidates included) this run coded from the coefficient lists (k_list_refine);
                                      0 with CSH_REF_LIST=0 and for sequential output */
+    uint32_t n_ac_in_lists;       /* components whose quantised AC levels this run did not store to the coefficient tiles: every coding kernel takes them from the coefficient
+                                     lists.  0 with CSH_AC_TILES=1 (and with any of CSH_NZ_FUSED=0, CSH_NZ_ONCE=0, CSH_TR_SORT=0, CSH_REF_LIST=0), in a re-quantisation run, for
+                                     sequential output, and for components counted out of n_fused_lists */
 } csh_timing;
 
 int csh_device_count(void);
@@ -172,7 +175,9 @@ int csh_batch_rerun_encode(csh_batch *b, csh_timing *t);
 
 /* stage taps for the parity tests (copy device intermediates to host after csh_batch_run):
    which = 0: decoded coefficients, 1: re-quantised coefficients.  dst receives the component's
-   [bh][bw][64] int16 blocks in ZIG-ZAG order.  Returns 0, or -1 (see csh_last_error). */
+   [bh][bw][64] int16 blocks in ZIG-ZAG order.  Returns 0, or -1 (see csh_last_error).
+   which = 1 materialises on demand: a component counted in csh_timing.n_ac_in_lists has only its DC in the tiles after a run, and the call first writes its AC
+   coefficients back from the coefficient lists (a small kernel on the batch's stream; calling it again gives the same, and a later run is not affected). */
 int csh_batch_geometry(csh_batch *b, size_t image, int comp, int which, int *bw, int *bh, int *real_bw, int *real_bh);
 int csh_batch_read_coefs(csh_batch *b, size_t image, int comp, int which, int16_t *dst);
 
