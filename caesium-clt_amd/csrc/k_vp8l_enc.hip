@@ -26,9 +26,6 @@ __device__ __forceinline__ static uint32_t sg_pixel(const Vp8lImg &im, uint32_t 
     const uint32_t r = p[0], g = p[1], b = p[2];
     return (nc == 4 ? uint32_t(p[3]) << 24 : 0xFF000000u) | (((r - g) & 255u) << 16) | (g << 8) | ((b - g) & 255u);
 }
-__device__ __forceinline__ static uint32_t lsub(uint32_t a, uint32_t b) {   // per-channel a - b mod 256
-    return (((a | 0x00FF00FFu) - (b & 0xFF00FF00u)) & 0xFF00FF00u) | (((a | 0xFF00FF00u) - (b & 0x00FF00FFu)) & 0x00FF00FFu);
-}
 __device__ __forceinline__ static uint32_t res_cost(uint32_t r) {   // sum over the channels of the residual's distance from 0 (mod 256)
     uint32_t c = 0;
     for (int s = 0; s < 32; s += 8) { const uint32_t v = (r >> s) & 255u; c += v < 128u ? v : 256u - v; }
@@ -50,7 +47,7 @@ __global__ void __launch_bounds__(256) k_vp8l_residuals(const Vp8lImg *imgs, uin
     CSH_SHARED uint32_t s_mode;
     const Vp8lImg &im = imgs[blockIdx.y];
     const uint32_t blk = blockIdx.x;
-    const uint32_t by = blk / im.bw, bx = blk - by * im.bw;
+    const uint32_t by = im.bw ? blk / im.bw : 0u, bx = blk - by * im.bw;   // (bw = 0: a palette candidate's record, which has no block)
     const uint32_t tid = threadIdx.x, x = bx * 16u + (tid & 15u), y = by * 16u + (tid >> 4);
     const bool inside = blk < im.bw * im.bh && x < im.width && y < im.height;
     CSH_PHASE_LOOP(4) {
@@ -106,8 +103,12 @@ struct PackLds {
     uint32_t win[160];
     Vp8lCodeUse use[5];
 };
+struct PackPalLds { Vp8lPalCodes pal; Vp8lDescLds desc; };   // a palette candidate's head (CSH_VP8L=palette)
 
-// pick: nullptr, or per picture four words of which the first says that the refs coder writes this picture's file (k_vp8l_refs.hip)
+// pick: nullptr, or per record four words of which the first is 0 where this kernel writes the file (k_vp8l_refs.hip, k_vp8l_palette.hip).
+// PAL: the records that are palette candidates, and only those -- no predictor: the head is the colour-indexing transform, the pixels are the bundled indices, the
+// file is the parent's.  (Two kernels: the pictures' one is the default coder's and stays the code it was.)
+template <bool PAL>
 __global__ void __launch_bounds__(CSP_WAVE_THREADS) k_vp8l_pack(const Vp8lImg *imgs, int nimg, const uint32_t *work, const uint8_t *modes, const uint32_t *hist, const uint32_t *pick, uint8_t *outp,
                                                                 uint32_t *file_len, uint32_t *status) {
     CSH_SHARED PackLds S;
@@ -115,6 +116,7 @@ __global__ void __launch_bounds__(CSP_WAVE_THREADS) k_vp8l_pack(const Vp8lImg *i
     if (image >= nimg) return;
     if (pick && pick[4 * image]) return;
     const Vp8lImg im = imgs[image];
+    if (PAL != (im.pal != nullptr)) return;
     uint8_t *file = outp + im.out_off;
     const uint32_t *hh = hist + uint64_t(image) * 1024u;
     const uint32_t nblk = im.bw * im.bh;
@@ -136,7 +138,11 @@ __global__ void __launch_bounds__(CSP_WAVE_THREADS) k_vp8l_pack(const Vp8lImg *i
     CSP_WAVE_SYNC();
     Vp8lPut P;
     P.begin(S.win, file + 20);
-    P.head(im, modes, S.len[3], S.code[3], S.use[3]);
+    if (PAL) {
+        CSH_SHARED PackPalLds SP;
+        vp8l_pal_codes(im.pal + 512, SP.pal);
+        P.head_palette(im, SP.pal, SP.desc);
+    } else P.head(im, modes, S.len[3], S.code[3], S.use[3]);
     P.put1(0, 1);                                   // the picture: no colour cache
     P.put1(0, 1);                                   // no meta prefix image
     P.code(S.len[0], S.use[0]); P.code(S.len[1], S.use[1]); P.code(S.len[2], S.use[2]); P.code(S.len[4], S.use[4]); P.single();   // green, red, blue, alpha (one symbol, no bits, in an opaque picture), distance
@@ -153,16 +159,22 @@ __global__ void __launch_bounds__(CSP_WAVE_THREADS) k_vp8l_pack(const Vp8lImg *i
         }
         P.bo.put(val, nb);
     }
-    P.finish(im, file, image, file_len, status);
+    P.finish(im, file, PAL ? int(im.parent) : image, file_len, status);
 }
 
+// (a palette candidate's record has bw = bh = 0: the residual kernel skips it, its index image is in work already; the counts are taken of every record)
 void launch_vp8l_front(hipStream_t st, const Vp8lImg *imgs, int nimg, uint32_t max_blocks, uint64_t max_pixels, uint32_t *work, uint8_t *modes, uint32_t *hist) {
     CSH_LAUNCH_PHASED(k_vp8l_residuals, 4, dim3(max_blocks, unsigned(nimg)), dim3(256), st, imgs, work, modes);
     CSH_LAUNCH_PHASED(k_vp8l_hist, 3, dim3(unsigned((max_pixels + 4095) / 4096), unsigned(nimg)), dim3(256), st, imgs, work, hist);
 }
 void launch_vp8l_pack_plain(hipStream_t st, const Vp8lImg *imgs, int nimg, const uint32_t *work, const uint8_t *modes, const uint32_t *hist, const uint32_t *pick, uint8_t *out, uint32_t *file_len,
                             uint32_t *status) {
-    CSH_LAUNCH(k_vp8l_pack, dim3(unsigned(nimg)), dim3(CSP_WAVE_THREADS), st, imgs, nimg, work, modes, hist, pick, out, file_len, status);
+    CSH_LAUNCH(k_vp8l_pack<false>, dim3(unsigned(nimg)), dim3(CSP_WAVE_THREADS), st, imgs, nimg, work, modes, hist, pick, out, file_len, status);
+}
+void launch_vp8l_pack_candidates(hipStream_t st, const Vp8lImg *imgs, int first, int nimg, const uint32_t *work, const uint8_t *modes, const uint32_t *hist, const uint32_t *pick, uint8_t *out,
+                                 uint32_t *file_len, uint32_t *status) {
+    if (nimg <= first) return;
+    CSH_LAUNCH(k_vp8l_pack<true>, dim3(unsigned(nimg - first)), dim3(CSP_WAVE_THREADS), st, imgs + first, nimg - first, work, modes, hist + uint64_t(first) * 1024u, pick + 4 * first, out, file_len, status);
 }
 void launch_vp8l_encode(hipStream_t st, const Vp8lImg *imgs, int nimg, uint32_t max_blocks, uint64_t max_pixels, uint32_t *work, uint8_t *modes, uint32_t *hist, uint8_t *out, uint32_t *file_len,
                         uint32_t *status) {

@@ -439,12 +439,13 @@ struct PackRefsLds {
     uint32_t win[160];
     Vp8lCodeUse use[6];
     Vp8lDescLds desc;
+    Vp8lPalCodes pal;   // a palette candidate's head (CSH_VP8L=palette)
 };
 __global__ void __launch_bounds__(CSP_WAVE_THREADS) k_vp8l_pack_refs(const Vp8lImg *imgs, int nimg, const uint32_t *work, const uint8_t *modes, const uint64_t *toks, const uint8_t *hits,
                                                                      const uint32_t *hist, const uint8_t *lens, const uint32_t *pick, uint8_t *outp, uint32_t *file_len, uint32_t *status) {
     CSH_SHARED PackRefsLds S;
     const int image = blockIdx.x;
-    if (image >= nimg || !pick[4 * image]) return;
+    if (image >= nimg || pick[4 * image] != 1u) return;
     const Vp8lImg im = imgs[image];
     uint8_t *file = outp + im.out_off;
     const uint32_t opt = pick[4 * image + 1], cbits = vp8l_cache_bits(opt);
@@ -475,7 +476,8 @@ __global__ void __launch_bounds__(CSP_WAVE_THREADS) k_vp8l_pack_refs(const Vp8lI
     CSP_WAVE_SYNC();
     Vp8lPut P;
     P.begin(S.win, file + 20);
-    P.head(im, modes, S.mlen, S.mcode, S.use[5]);
+    if (im.pal) { vp8l_pal_codes(im.pal + 512, S.pal); P.head_palette(im, S.pal, S.desc); }   // the bundled indices of picture im.parent: width is the packed width
+    else P.head(im, modes, S.mlen, S.mcode, S.use[5]);
     if (cbits) P.put1(1u | (uint64_t(cbits) << 1), 5); else P.put1(0, 1);   // the picture's colour cache
     P.put1(0, 1);                                                              // no meta prefix image
     P.code_runs(S.glen, int(vp8l_alphabet(0, opt)), S.use[0], S.desc);
@@ -511,12 +513,10 @@ __global__ void __launch_bounds__(CSP_WAVE_THREADS) k_vp8l_pack_refs(const Vp8lI
         }
         P.bo.put(val, nb);
     }
-    P.finish(im, file, image, file_len, status);
+    P.finish(im, file, im.pal ? int(im.parent) : image, file_len, status);
 }
 
-void launch_vp8l_encode_refs(hipStream_t st, const Vp8lImg *imgs, int nimg, uint32_t max_blocks, uint64_t max_pixels, uint32_t *work, uint8_t *modes, uint32_t *hist, const Vp8lRefs &R,
-                             uint8_t *out, uint32_t *file_len, uint32_t *status) {
-    if (!nimg) return;
+void launch_vp8l_refs_stages(hipStream_t st, const Vp8lImg *imgs, int nimg, uint32_t max_blocks, uint64_t max_pixels, uint32_t *work, uint8_t *modes, uint32_t *hist, const Vp8lRefs &R) {
     const unsigned max_chunks = unsigned((max_pixels + VP8L_CHUNK - 1) / VP8L_CHUNK);
     launch_vp8l_front(st, imgs, nimg, max_blocks, max_pixels, work, modes, hist);
     CSH_LAUNCH(k_vp8l_match, dim3(max_chunks, unsigned(nimg)), dim3(CSP_WAVE_THREADS), st, imgs, work, R.tok);
@@ -526,8 +526,17 @@ void launch_vp8l_encode_refs(hipStream_t st, const Vp8lImg *imgs, int nimg, uint
     CSH_LAUNCH(k_vp8l_cache_hits, dim3(max_chunks, unsigned(nimg)), dim3(CSP_WAVE_THREADS), st, imgs, work, R.cst, R.hit);
     CSH_LAUNCH_PHASED(k_vp8l_refs_hist, 3, dim3(max_chunks, unsigned(nimg)), dim3(256), st, imgs, work, R.tok, R.hit, R.hist);
     CSH_LAUNCH(k_vp8l_refs_codes, dim3(unsigned(nimg)), dim3(CSP_WAVE_THREADS), st, imgs, nimg, hist, R.hist, R.lens, R.pick);
+}
+void launch_vp8l_refs_packs(hipStream_t st, const Vp8lImg *imgs, int nimg, const uint32_t *work, const uint8_t *modes, const uint32_t *hist, const Vp8lRefs &R, uint8_t *out, uint32_t *file_len,
+                            uint32_t *status) {
     CSH_LAUNCH(k_vp8l_pack_refs, dim3(unsigned(nimg)), dim3(CSP_WAVE_THREADS), st, imgs, nimg, work, modes, R.tok, R.hit, R.hist, R.lens, R.pick, out, file_len, status);
     launch_vp8l_pack_plain(st, imgs, nimg, work, modes, hist, R.pick, out, file_len, status);
+}
+void launch_vp8l_encode_refs(hipStream_t st, const Vp8lImg *imgs, int nimg, uint32_t max_blocks, uint64_t max_pixels, uint32_t *work, uint8_t *modes, uint32_t *hist, const Vp8lRefs &R,
+                             uint8_t *out, uint32_t *file_len, uint32_t *status) {
+    if (!nimg) return;
+    launch_vp8l_refs_stages(st, imgs, nimg, max_blocks, max_pixels, work, modes, hist, R);
+    launch_vp8l_refs_packs(st, imgs, nimg, work, modes, hist, R, out, file_len, status);
 }
 
 }  // namespace csw

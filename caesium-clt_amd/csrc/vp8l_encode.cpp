@@ -23,11 +23,13 @@ extern "C" int csl_encode_pixels(const csp_pixels *px, size_t count, int device,
         return int(count);
     }
     // the coder, read on every call: unset / empty / "plain" = literals only (the bytes oracle/png_oracle.c cso_vp8l_encode states), "refs" = backward
-    // references and a colour cache (k_vp8l_refs.hip)
+    // references and a colour cache (k_vp8l_refs.hip), "palette" = refs, and for a picture of at most 256 colours the colour-indexing transform where that is
+    // smaller (k_vp8l_palette.hip)
     const char *mode = getenv("CSH_VP8L");
-    const bool refs = mode && !strcmp(mode, "refs");
+    const bool palette = mode && !strcmp(mode, "palette");
+    const bool refs = palette || (mode && !strcmp(mode, "refs"));
     if (mode && *mode && !refs && strcmp(mode, "plain")) {
-        for (size_t i = 0; i < count; i++) results[i] = make_res(CS_ERR_UNSUPPORTED, "CSH_VP8L names no lossless WebP coder (plain, refs)");
+        for (size_t i = 0; i < count; i++) results[i] = make_res(CS_ERR_UNSUPPORTED, "CSH_VP8L names no lossless WebP coder (plain, refs, palette)");
         return int(count);
     }
     int failed = 0;
@@ -65,25 +67,58 @@ extern "C" int csl_encode_pixels(const csp_pixels *px, size_t count, int device,
     DevBuf<uint32_t> d_work, d_hist, d_len, d_status;
     DevBuf<uint8_t> d_modes, d_out, d_hit, d_lens;
     DevBuf<uint64_t> d_tok, d_cst;
-    DevBuf<uint32_t> d_rhist, d_pick;
+    DevBuf<uint32_t> d_rhist, d_pick, d_pcount, d_pal;
+    DevBuf<unsigned long long> d_ptab;
     std::vector<uint32_t> len(imgs.size()), status(imgs.size());
     bool ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
     have_st = ok;
+    // palette: the colours of every picture are counted first, and the one read-back of the counts (4 bytes per picture) decides which pictures get a candidate
+    // record and pools of their own, behind the pictures'
+    const size_t nparent = imgs.size();
+    uint64_t max_packed = 0;
+    if (ok && palette) {
+        std::vector<uint32_t> pcount(nparent);
+        ok = !d_imgs.upload(imgs, st) && !d_ptab.alloc(nparent * csw::VP8L_PAL_SLOTS + 8) && !d_ptab.zero(st) && !d_pcount.alloc(nparent + 1) && !d_pcount.zero(st);
+        if (ok) {
+            csw::launch_vp8l_pal_count(st, d_imgs.p, int(nparent), max_px, d_ptab.p, d_pcount.p);
+            ok = csh_copy_wait(pcount.data(), d_pcount.p, nparent * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess && hipGetLastError() == hipSuccess;
+        }
+        for (size_t k = 0; ok && k < nparent; k++) {
+            if (pcount[k] < 1 || pcount[k] > csw::VP8L_PAL_MAX) continue;
+            csw::Vp8lImg im = imgs[k];
+            im.pal_n = pcount[k]; im.parent = uint32_t(k); im.src_width = im.width;
+            im.width = (im.width + (1u << csw::vp8l_pal_bits(im.pal_n)) - 1) >> csw::vp8l_pal_bits(im.pal_n);
+            im.bw = im.bh = 0; im.mode_off = 0;
+            const uint64_t npx = uint64_t(im.width) * im.height;
+            im.res_off = work; work += (npx + 63) & ~uint64_t(63);
+            im.nchunk = uint32_t((npx + csw::VP8L_CHUNK - 1) / csw::VP8L_CHUNK);
+            im.tok_off = im.res_off; im.hit_off = im.res_off;
+            im.cst_off = cst; cst += uint64_t(im.nchunk) * csw::VP8L_CACHE_STATE;
+            max_packed = std::max(max_packed, npx);
+            imgs.push_back(im);
+        }
+        const size_t ncand = imgs.size() - nparent;
+        ok = ok && !d_pal.alloc(ncand * csw::VP8L_PAL_BLOCK + 8);
+        for (size_t k = 0; ok && k < ncand; k++) imgs[nparent + k].pal = d_pal.p + k * csw::VP8L_PAL_BLOCK;
+    }
     ok = ok && !d_imgs.upload(imgs, st) && !d_work.alloc(work + 64) && !d_hist.alloc(imgs.size() * 1024 + 8) && !d_hist.zero(st) && !d_len.alloc(imgs.size() + 1) && !d_status.alloc(imgs.size() + 1) &&
          !d_modes.alloc(modes + 64) && !d_out.alloc(out + 256);
     if (ok && refs)
         ok = !d_tok.alloc(work + 64) && !d_hit.alloc(work + 64) && !d_cst.alloc(cst + 64) && !d_rhist.alloc(imgs.size() * csw::VP8L_NOPT * csw::VP8L_HIST + 8) && !d_rhist.zero(st) &&
              !d_lens.alloc(imgs.size() * csw::VP8L_LENS + 8) && !d_pick.alloc(imgs.size() * 4 + 4);
     if (ok) {
-        if (refs) {
-            const csw::Vp8lRefs pools = {d_tok.p, d_hit.p, d_cst.p, d_rhist.p, d_lens.p, d_pick.p};
+        const csw::Vp8lRefs pools = {d_tok.p, d_hit.p, d_cst.p, d_rhist.p, d_lens.p, d_pick.p};
+        if (palette)
+            csw::launch_vp8l_encode_palette(st, d_imgs.p, int(nparent), int(imgs.size() - nparent), max_blocks, max_px, max_packed, d_ptab.p, d_pal.p, d_work.p, d_modes.p, d_hist.p, pools, d_out.p,
+                                            d_len.p, d_status.p);
+        else if (refs)
             csw::launch_vp8l_encode_refs(st, d_imgs.p, int(imgs.size()), max_blocks, max_px, d_work.p, d_modes.p, d_hist.p, pools, d_out.p, d_len.p, d_status.p);
-        } else
+        else
             csw::launch_vp8l_encode(st, d_imgs.p, int(imgs.size()), max_blocks, max_px, d_work.p, d_modes.p, d_hist.p, d_out.p, d_len.p, d_status.p);
         ok = hipMemcpyAsync(len.data(), d_len.p, len.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
              hipMemcpyAsync(status.data(), d_status.p, status.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess && hipGetLastError() == hipSuccess;
     }
-    for (size_t k = 0; k < imgs.size(); k++) {
+    for (size_t k = 0; k < nparent; k++) {
         const size_t i = at[k];
         if (!ok) { results[i] = make_res(CS_ERR_NO_DEVICE, "lossless WebP coding failed on the device"); failed++; continue; }
         if (status[k] || !len[k]) { results[i] = make_res(CS_ERR_POOL_OVERFLOW, "lossless WebP output larger than its region"); failed++; continue; }

@@ -9,6 +9,9 @@ namespace csw {
 
 using csp::LV;
 
+__device__ __forceinline__ static uint32_t lsub(uint32_t a, uint32_t b) {   // per-channel a - b mod 256
+    return (((a | 0x00FF00FFu) - (b & 0xFF00FF00u)) & 0xFF00FF00u) | (((a | 0xFF00FF00u) - (b & 0x00FF00FFu)) & 0x00FF00FFu);
+}
 __device__ __forceinline__ static uint32_t rev4(uint32_t v) { return ((v & 1u) << 3) | ((v & 2u) << 1) | ((v & 4u) >> 1) | ((v & 8u) >> 3); }
 
 // one prefix code as the stream describes it: symbols with a non-zero count, the first two of them, the highest
@@ -72,6 +75,26 @@ __device__ __forceinline__ static uint32_t vp8l_refs_desc_bits(const uint8_t *le
     return vp8l_length_code(len, n, L);
 }
 struct Vp8lDescLds { Vp8lLengthCode L; uint32_t ntok; uint16_t tok[VP8L_GREEN_MAX]; };   // the pack kernel's room for one description: symbol | extra << 8
+
+// ---- the palette's sub-image (CSH_VP8L=palette): its four codes from its counts (VP8L_PAL_HIST), one lane each, and the exact bits of its descriptions and pixels
+struct Vp8lPalCodes { uint8_t len[4][288]; uint16_t code[4][288]; Vp8lCodeUse use[4]; uint32_t bits[4]; };
+__device__ __forceinline__ static int vp8l_pal_alphabet(int c) { return c == 0 ? 280 : 256; }
+__device__ __forceinline__ static void vp8l_pal_codes(const uint32_t *hist, Vp8lPalCodes &C) {
+    LFOR(l) if (l < 4) {
+        const int n = vp8l_pal_alphabet(l);
+        const uint32_t *f = hist + (l == 0 ? 0 : 288 + 256 * (l - 1));
+        csp::code_lengths(f, n, 15, C.len[l]);
+        const Vp8lCodeUse u = vp8l_code_use([&](int i) { return f[i]; }, n);
+        if (u.nused <= 1) for (int i = 0; i < n; i++) C.len[l][i] = 0;   // a code with one symbol costs no bits
+        csp::canonical(C.len[l], n, C.code[l]);
+        uint32_t b = vp8l_refs_desc_bits(C.len[l], n, u);
+        for (int i = 0; i < n; i++) b += f[i] * C.len[l][i];
+        C.use[l] = u; C.bits[l] = b;
+    }
+    CSP_WAVE_SYNC();
+}
+// bits of a candidate's head behind the sizes: the transform (1 + 2 + 8), the sub-image ("no cache", five descriptions, the entries), "no further transform"
+__device__ __forceinline__ static uint32_t vp8l_pal_head_bits(const Vp8lPalCodes &C) { return 11u + 1u + C.bits[0] + C.bits[1] + C.bits[2] + C.bits[3] + 4u + 1u; }
 
 struct Vp8lPut {
     csp::BitOut bo;
@@ -153,7 +176,30 @@ struct Vp8lPut {
         }
         put1(0, 1);                                   // no further transform
     }
-    // the last bits, then the RIFF framing in front of the payload (which starts at file + 20)
+    // a candidate's head: signature, the PICTURE's sizes, the colour-indexing transform with its palette as a sub-image, "no further transform"
+    __device__ __forceinline__ void head_palette(const Vp8lImg &im, const Vp8lPalCodes &C, Vp8lDescLds &D) {
+        put1(0x2F, 8);
+        const bool has_alpha = im.channels == 2 || im.channels == 4;
+        put1(uint64_t(im.src_width - 1) | (uint64_t(im.height - 1) << 14) | (uint64_t(has_alpha ? 1 : 0) << 28) | (0ull << 29), 32);
+        put1(1 | (3u << 1) | (uint64_t(im.pal_n - 1) << 3), 11);   // a transform follows: colour indexing, the number of colours minus one
+        put1(0, 1);                                                 // the sub-image: no colour cache
+        for (int c = 0; c < 4; c++) code_runs(C.len[c], vp8l_pal_alphabet(c), C.use[c], D);
+        single();                                                   // green, red, blue, alpha, distance
+        const uint32_t *sub = im.pal + 256;
+        for (uint32_t i0 = 0; i0 < im.pal_n; i0 += 64) {
+            LV<uint64_t> val; LV<uint32_t> nb;
+            LFOR(l) {
+                const uint32_t i = i0 + uint32_t(l), v = i < im.pal_n ? sub[i] : 0u;
+                const uint32_t g = (v >> 8) & 255u, r = (v >> 16) & 255u, b = v & 255u, a = v >> 24;
+                const uint32_t lg = C.len[0][g], lr = C.len[1][r], lb = C.len[2][b], la = C.len[3][a];
+                nb[l] = i < im.pal_n ? lg + lr + lb + la : 0u;
+                val[l] = uint64_t(C.code[0][g]) | (uint64_t(C.code[1][r]) << lg) | (uint64_t(C.code[2][b]) << (lg + lr)) | (uint64_t(C.code[3][a]) << (lg + lr + lb));
+            }
+            bo.put(val, nb);
+        }
+        put1(0, 1);                                                 // no further transform
+    }
+    // the last bits, then the RIFF framing in front of the payload (which starts at file + 20).  image: the picture's entry (a candidate's: its parent's)
     __device__ __forceinline__ void finish(const Vp8lImg &im, uint8_t *file, int image, uint32_t *file_len, uint32_t *status) {
         const uint64_t payload = (bo.bitpos + 7) >> 3;
         bo.finish();

@@ -49,6 +49,12 @@ struct Vp8lImg {
     uint64_t tok_off;      // one u64 per pixel (u64 index into the token pool): the match candidate, then the parse's token
     uint64_t hit_off;      // one byte per pixel: bit k = the pixel hits the colour cache of option k (vp8l_cache_bits)
     uint64_t cst_off;      // colour-cache contents in front of every chunk, every option (u64 index): nchunk x VP8L_CACHE_STATE
+    // CSH_VP8L=palette only (k_vp8l_palette.hip), and only in a CANDIDATE record: the bundled palette indices of picture `parent` as one more picture for the
+    // refs stages.  width is then the packed width, bw = bh = 0 (no predictor: the front end's residual kernel has no block of it), out_off / out_cap the parent's
+    const uint32_t *pal;   // this candidate's VP8L_PAL_BLOCK words (nullptr: a picture)
+    uint32_t pal_n;        // colours, 1 .. 256
+    uint32_t parent;       // the picture's record: its file region, its file_len / status entry
+    uint32_t src_width;    // the picture's width
 };
 void launch_vp8l_encode(hipStream_t st, const Vp8lImg *imgs, int nimg, uint32_t max_blocks, uint64_t max_pixels, uint32_t *work, uint8_t *modes, uint32_t *hist, uint8_t *out, uint32_t *file_len,
                         uint32_t *status);
@@ -70,10 +76,34 @@ struct Vp8lRefs {
     uint64_t *cst;         // cache contents (cst_off)
     uint32_t *hist;        // per picture VP8L_NOPT x VP8L_HIST counts, zeroed by the caller
     uint8_t *lens;         // per picture VP8L_LENS
-    uint32_t *pick;        // per picture 4 words: 1 = the refs stream is smaller, the option, the two streams' bits behind the common header
+    uint32_t *pick;        // per record 4 words: who writes (0 the plain pack, 1 the refs pack, 2 neither: another record of the picture does), the option, the two streams' bits behind the head
 };
 void launch_vp8l_encode_refs(hipStream_t st, const Vp8lImg *imgs, int nimg, uint32_t max_blocks, uint64_t max_pixels, uint32_t *work, uint8_t *modes, uint32_t *hist, const Vp8lRefs &refs,
                              uint8_t *out, uint32_t *file_len, uint32_t *status);
+// the two halves of launch_vp8l_encode_refs, for a caller that looks at pick in between (k_vp8l_palette.hip): everything up to the codes and pick; the two packs
+void launch_vp8l_refs_stages(hipStream_t st, const Vp8lImg *imgs, int nimg, uint32_t max_blocks, uint64_t max_pixels, uint32_t *work, uint8_t *modes, uint32_t *hist, const Vp8lRefs &refs);
+void launch_vp8l_refs_packs(hipStream_t st, const Vp8lImg *imgs, int nimg, const uint32_t *work, const uint8_t *modes, const uint32_t *hist, const Vp8lRefs &refs, uint8_t *out, uint32_t *file_len,
+                            uint32_t *status);
+// the colour-indexing transform (CSH_VP8L=palette, k_vp8l_palette.hip).  A picture with at most VP8L_PAL_MAX distinct ARGB values gets a candidate record behind
+// the pictures' records; the smallest of the picture's plain stream, its refs stream and the candidate's is written
+enum : uint32_t {
+    VP8L_PAL_MAX = 256,                   // the format's largest palette
+    VP8L_PAL_SLOTS = 1024,                // hash slots of the colour count, per picture (u64 each: bit 32 = in use, the low word the ARGB)
+    VP8L_PAL_STRIP = 16384,               // pixels per wave of the colour count
+    VP8L_PAL_HIST = 288 + 3 * 256 + 40,   // counts of the palette's sub-image: green (as an alphabet of 280), red, blue, alpha, distance (none)
+    VP8L_PAL_BLOCK = 2 * 256 + VP8L_PAL_HIST,   // per candidate: the palette ascending, its sub-image (entry minus predecessor), the counts
+};
+__host__ __device__ static inline uint32_t vp8l_pal_bits(uint32_t n) { return n <= 2 ? 3u : n <= 4 ? 2u : n <= 16 ? 1u : 0u; }   // 1 << bits indices per packed pixel
+// count[i] of picture i < nimg: its distinct ARGB values if there are at most VP8L_PAL_MAX, something larger otherwise.  tabs: nimg x VP8L_PAL_SLOTS, zeroed like count
+void launch_vp8l_pal_count(hipStream_t st, const Vp8lImg *imgs, int nimg, uint64_t max_pixels, unsigned long long *tabs, uint32_t *count);
+// imgs: nparent pictures, then ncand candidates (in the order of their parents).  Sorts the palettes, writes the candidates' index images into work, runs the refs
+// stages over all the records, chooses per picture and packs
+void launch_vp8l_encode_palette(hipStream_t st, const Vp8lImg *imgs, int nparent, int ncand, uint32_t max_blocks, uint64_t max_pixels, uint64_t max_packed, const unsigned long long *tabs,
+                                uint32_t *pal, uint32_t *work, uint8_t *modes, uint32_t *hist, const Vp8lRefs &refs, uint8_t *out, uint32_t *file_len, uint32_t *status);
+// the literals-only stream of the candidates first .. nimg - 1 whose pick[4 i] is 0 (k_vp8l_enc.hip: the plain pack with the palette's head; launch_vp8l_pack_plain
+// itself passes candidates by)
+void launch_vp8l_pack_candidates(hipStream_t st, const Vp8lImg *imgs, int first, int nimg, const uint32_t *work, const uint8_t *modes, const uint32_t *hist, const uint32_t *pick, uint8_t *out,
+                                 uint32_t *file_len, uint32_t *status);
 // pieces of launch_vp8l_encode (k_vp8l_enc.hip) the refs coder runs as they are: the front end, and the plain pack for the pictures whose pick[4 i] is 0 (pick = nullptr: all)
 void launch_vp8l_front(hipStream_t st, const Vp8lImg *imgs, int nimg, uint32_t max_blocks, uint64_t max_pixels, uint32_t *work, uint8_t *modes, uint32_t *hist);
 void launch_vp8l_pack_plain(hipStream_t st, const Vp8lImg *imgs, int nimg, const uint32_t *work, const uint8_t *modes, const uint32_t *hist, const uint32_t *pick, uint8_t *out, uint32_t *file_len,

@@ -1,9 +1,11 @@
-"""Time csl_encode_pixels (pixels in device memory -> lossless WebP files) in both coders, in one process: CSH_VP8L=plain (literals only) against CSH_VP8L=refs
-(backward references and a colour cache).  96 pictures of 1920 x 1080 by default: photographic (three textures) and graphic content, repeated.
+"""Time csl_encode_pixels (pixels in device memory -> lossless WebP files) in its coders, in one process: CSH_VP8L=plain (literals only), CSH_VP8L=refs
+(backward references and a colour cache), CSH_VP8L=palette (refs, and the colour-indexing transform for pictures of at most 256 colours).  96 pictures of
+1920 x 1080 by default: photographic (three textures) and graphic content, repeated.
 
-    python tools/vp8l_refs_time.py [--count 96] [--width 1920] [--height 1080] [--repeats 3] [--once] [--modes plain,refs]
+    python tools/vp8l_refs_time.py [--count 96] [--width 1920] [--height 1080] [--repeats 3] [--once] [--modes plain,refs] [--dithered 0]
 
---once: one call per mode after the warm-up (what a kernel trace wants); --modes: one coder alone.  Prints one line per call and a summary."""
+--once: one call per mode after the warm-up (what a kernel trace wants); --modes: the coders to run, the first is what the others are compared with;
+--dithered K: K more pictures, texture 5 dithered to 16 colours (Floyd-Steinberg), behind the mix.  Prints one line per call and a summary."""
 import argparse
 import ctypes as C
 import os
@@ -43,6 +45,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--once", action="store_true")
     ap.add_argument("--modes", default="plain,refs")
+    ap.add_argument("--dithered", type=int, default=0)
     a = ap.parse_args()
     pkg = package()
     api = pkg.load()
@@ -50,10 +53,15 @@ def main():
     from caesium_clt_amd.binding import CByteArray, CCSResult
     base = [torch.from_numpy(np.ascontiguousarray(p)).cuda() for p in pictures(a.width, a.height)]
     torch.cuda.synchronize()
-    n = a.count
+    n = a.count + a.dithered
     px = (Pixels * n)()
+    if a.dithered:
+        from PIL import Image
+        d16 = Image.fromarray(synth_rgb(2, a.width, a.height, texture=5.0)).quantize(16, dither=Image.Dither.FLOYDSTEINBERG).convert("RGB")
+        dith = torch.from_numpy(np.ascontiguousarray(np.asarray(d16))).cuda()
+        torch.cuda.synchronize()
     for i in range(n):
-        px[i].device_pixels, px[i].width, px[i].height, px[i].channels = base[i % len(base)].data_ptr(), a.width, a.height, 3
+        px[i].device_pixels, px[i].width, px[i].height, px[i].channels = (base[i % len(base)] if i < a.count else dith).data_ptr(), a.width, a.height, 3
     api.L.csl_encode_pixels.argtypes = [C.POINTER(Pixels), C.c_size_t, C.c_int, C.POINTER(CByteArray), C.POINTER(CCSResult)]
     api.L.csl_encode_pixels.restype = C.c_int
 
@@ -77,16 +85,16 @@ def main():
         for mode in modes:
             dt, sizes[mode] = call(mode)
             times[mode].append(dt)
-            print("call %d %-5s %8.1f ms  %d bytes" % (r, mode, dt * 1e3, sum(sizes[mode])), flush=True)
+            print("call %d %-7s %8.1f ms  %d bytes" % (r, mode, dt * 1e3, sum(sizes[mode])), flush=True)
     mp = n * a.width * a.height / 1e6
     for mode in modes:
         best = min(times[mode])
-        print("%-5s best of %d: %8.1f ms for %d x %dx%d (%.0f MP/s), %d bytes" % (mode, len(times[mode]), best * 1e3, n, a.width, a.height, mp / best, sum(sizes[mode])))
-    if len(modes) < 2:
-        return
-    print("refs / plain: time %.2f, bytes %.3f" % (min(times["refs"]) / min(times["plain"]), sum(sizes["refs"]) / sum(sizes["plain"])))
-    k = len(base)
-    print("per picture kind (bytes plain -> refs):", ", ".join("%d -> %d" % (sizes["plain"][i], sizes["refs"][i]) for i in range(min(k, n))))
+        print("%-7s best of %d: %8.1f ms, spread %.1f ms, for %d x %dx%d (%.0f MP/s), %d bytes" % (mode, len(times[mode]), best * 1e3, (max(times[mode]) - best) * 1e3, n, a.width,
+                                                                                                    a.height, mp / best, sum(sizes[mode])))
+    kinds = list(range(min(len(base), a.count))) + ([a.count] if a.dithered else [])
+    for mode in modes[1:]:
+        print("%s / %s: time %.2f, bytes %.3f" % (mode, modes[0], min(times[mode]) / min(times[modes[0]]), sum(sizes[mode]) / sum(sizes[modes[0]])))
+        print("per picture kind (bytes %s -> %s):" % (modes[0], mode), ", ".join("%d -> %d" % (sizes[modes[0]][i], sizes[mode][i]) for i in kinds))
 
 
 if __name__ == "__main__":
