@@ -84,7 +84,7 @@ struct PixelPlan {
 
 // a contiguous range of everything the coding kernels index: work items, slots, token chunks, tables, plans, list builder chunks, slot lists
 struct Stage {
-    uint32_t work0 = 0, nwork = 0, slot0 = 0, nslots = 0, ech0 = 0, nech = 0, table0 = 0, ntables = 0, plan0 = 0, nplans = 0, nzc0 = 0, nnzc = 0, ls0 = 0, nls = 0, ts0 = 0, nts = 0, rs0 = 0, nrs = 0;
+    uint32_t work0 = 0, nwork = 0, slot0 = 0, nslots = 0, ech0 = 0, nech = 0, table0 = 0, ntables = 0, plan0 = 0, nplans = 0, nzc0 = 0, nnzc = 0, ls0 = 0, nls = 0, ts0 = 0, nts = 0, rs0 = 0, nrs = 0, lr0 = 0, nlr = 0, rr0 = 0, nrr = 0;
     // does some NzChunk of the stage ask for level 0 from the tiles (k_nzlist) / for a filtered level (k_nzfilter)?  [0]: as planned (EncodePlan::nzchunks), [1]: in a run whose forward-DCT kernels built lists (nzchunks_fused)
     bool nz_build[2] = {true, true}, nz_filter[2] = {true, true};
 };
@@ -105,6 +105,10 @@ struct EncodePlan {
     uint32_t nslots = 0, nlist_slots = 0, ntok_slots = 0;
     uint32_t nref_slots = 0;              // those of the token-coded slots whose tokens k_list_refine makes (refinement scans coded from their list)
     uint32_t last_run_refine = 0;         // refinement work items the last run coded from lists (csh_timing.n_list_refine)
+    // k_list_stats, k_list_pack and k_list_refine take one wave per run of up to list_run consecutive chunks of a work item: the runs are counted beside the slots
+    uint32_t list_run = CSH_LIST_RUN;     // PlanSwitches::list_run
+    uint32_t nlist_runs = 0, nref_runs = 0;
+    uint32_t last_run_list_runs = 0;      // list and refinement runs of the work items the last run coded, all stages (csh_timing.n_list_runs)
     uint64_t total_corr = 0;              // correction words: one per unit of a refinement scan
     uint64_t total_units = 0, total_words = 0;
     uint32_t max_units = 0;
@@ -148,12 +152,12 @@ struct EncodePlan {
     Stage stage[ST_N];
     void stage_begin(Stage &sg) {
         sg.work0 = uint32_t(swork.size()); sg.slot0 = nslots; sg.ech0 = uint32_t(echunks.size()); sg.table0 = uint32_t(ntables); sg.plan0 = uint32_t(plans.size());
-        sg.nzc0 = uint32_t(nzchunks.size()); sg.ls0 = nlist_slots; sg.ts0 = ntok_slots; sg.rs0 = nref_slots;
+        sg.nzc0 = uint32_t(nzchunks.size()); sg.ls0 = nlist_slots; sg.ts0 = ntok_slots; sg.rs0 = nref_slots; sg.lr0 = nlist_runs; sg.rr0 = nref_runs;
     }
     void stage_end(Stage &sg) {
         sg.nwork = uint32_t(swork.size()) - sg.work0; sg.nslots = nslots - sg.slot0; sg.nech = uint32_t(echunks.size()) - sg.ech0;
         sg.ntables = uint32_t(ntables) - sg.table0; sg.nplans = uint32_t(plans.size()) - sg.plan0;
-        sg.nnzc = uint32_t(nzchunks.size()) - sg.nzc0; sg.nls = nlist_slots - sg.ls0; sg.nts = ntok_slots - sg.ts0; sg.nrs = nref_slots - sg.rs0;
+        sg.nnzc = uint32_t(nzchunks.size()) - sg.nzc0; sg.nls = nlist_slots - sg.ls0; sg.nts = ntok_slots - sg.ts0; sg.nrs = nref_slots - sg.rs0; sg.nlr = nlist_runs - sg.lr0; sg.nrr = nref_runs - sg.rr0;
     }
     std::vector<SearchImg> simg;
     std::vector<uint8_t> work_active;               // per work item: coded in the (gated) stage about to run
@@ -179,7 +183,7 @@ struct EncodePlan {
     DevBuf<NzList> d_nzlists;
     DevBuf<NzSet> d_nzsets;
     DevBuf<NzChunk> d_nzchunks, d_nzchunks_fused;
-    DevBuf<uint32_t> d_nz_pool, d_nz_cursor, d_nz_chunk_off, d_nz_chunk_cnt, d_list_slots, d_tok_slots, d_ref_slots;
+    DevBuf<uint32_t> d_nz_pool, d_nz_cursor, d_nz_chunk_off, d_nz_chunk_cnt, d_list_slots, d_tok_slots, d_ref_slots, d_list_runs, d_ref_runs;
 };
 
 // mozjpeg's quantiser half (CSH_PROFILE=mozjpeg): overshoot deringing in front of every forward DCT; trellis quantisation behind it --
@@ -307,6 +311,7 @@ struct PlanSwitches {
     bool fused_420 = true;      // CSH_NO_FUSED_420 unset
     bool nz_fused = true;       // CSH_NZ_FUSED != "0": the forward-DCT kernels build the level-0 coefficient lists
     bool ref_list = true;       // CSH_REF_LIST != "0": the AC refinement scans are coded from the coefficient lists (k_list_refine), not from the tiles (k_tokens' kind-0 chunks)
+    uint32_t list_run = CSH_LIST_RUN;   // CSH_LIST_RUN, clamped to 1..32: chunks per wave of k_list_stats, k_list_pack and k_list_refine (1: one wave per chunk)
     bool ac_tiles = false;      // CSH_AC_TILES == "1": every component's AC levels are stored to its tiles, as before they lived in the lists
     static PlanSwitches read();
 };

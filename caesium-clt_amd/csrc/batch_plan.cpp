@@ -241,6 +241,7 @@ PlanSwitches PlanSwitches::read() {
     const char *pp = getenv("CSH_PROG_PAR");
     s.prog_par = pp && !strcmp(pp, "0") ? 0 : (pp && !strcmp(pp, "1") ? 1 : -1);
     s.fused_420 = !getenv("CSH_NO_FUSED_420");
+    if (const char *lr = getenv("CSH_LIST_RUN")) { if (*lr) s.list_run = uint32_t(std::min(32, std::max(1, atoi(lr)))); }
     return s;
 }
 
@@ -265,6 +266,7 @@ void BatchPlanner::begin() {
     b->q_base = int(b->quants.size()) - 1;   // then one table per quality 1..100 (size targeting re-targets per image)
     for (int q = 1; q <= 100; q++) { uint16_t tq[64]; quality_table(q, tq); DevQuant dq; make_quant(tq, dq); b->quants.push_back(dq); }
     b->progressive = progressive;
+    b->enc.list_run = sw.list_run;
 
     add_script(b->enc.script, 3, true);   // entries 0..9
     add_script(b->enc.script, 1, true);   // entries 10..15
@@ -378,7 +380,7 @@ void BatchPlanner::add_works(Item &it, ImgDesc &im, int img_index, const std::ve
         // scans through tokens k_list_refine makes from it (CSH_REF_LIST=0: through k_tokens' kind-0 chunks, from the tiles); everything else from tokens
         const bool from_list = e.Ss > 0 && !e.sequential && e.Ah == 0;
         const bool ref_list = sw.ref_list && e.Ss > 0 && !e.sequential && e.Ah != 0;
-        w.list = 0xFFFFFFFFu; w.rs_base = 0xFFFFFFFFu;
+        w.list = 0xFFFFFFFFu; w.rs_base = 0xFFFFFFFFu; w.lr_base = 0xFFFFFFFFu; w.rr_base = 0xFFFFFFFFu;
         if (from_list || ref_list) {
             if (e.Al >= CSH_NZ_LEVELS) { it.code = CS_ERR_JPEG_FEATURE; it.msg = "internal: output scan script outside what the list coder carries"; }
             else {
@@ -405,6 +407,10 @@ void BatchPlanner::add_works(Item &it, ImgDesc &im, int img_index, const std::ve
             uint32_t &cursor = (from_list && w.list != 0xFFFFFFFFu) ? b->enc.nlist_slots : b->enc.ntok_slots;
             w.ls_base = cursor; cursor += nch;
             if (ref_list && w.list != 0xFFFFFFFFu) { w.rs_base = b->enc.nref_slots; b->enc.nref_slots += nch; }
+            // ... and its runs of up to list_run chunks, one wave of the list kernels each
+            const uint32_t nruns = (nch + b->enc.list_run - 1) / b->enc.list_run;
+            if (from_list && w.list != 0xFFFFFFFFu) { w.lr_base = b->enc.nlist_runs; b->enc.nlist_runs += nruns; }
+            if (ref_list && w.list != 0xFFFFFFFFu) { w.rr_base = b->enc.nref_runs; b->enc.nref_runs += nruns; }
         }
         if (e.Ss == 0 || e.sequential) {   // DC scans and sequential-mode scans: one token workgroup per (scan, 256 units)
             // tokens of a DC scan are known exactly (one per block, or one per fifteen blocks' bits); a sequential-mode block has at most 64 + 3
@@ -1171,7 +1177,7 @@ int BatchPlanner::upload(Laps &laps) {
         b->enc.d_tok_off.alloc(4 * size_t(b->enc.nslots) + 4) || b->enc.d_chunk_ntok.alloc(4 * size_t(b->enc.nslots) + 4) || b->enc.d_slot_hist.alloc(size_t(b->enc.hist_rows) * 256 + 256) ||
         b->enc.d_slot_raw.alloc(size_t(b->enc.nslots) + 1) || b->enc.d_img_list.upload(b->enc.img_list, st) || b->enc.d_img_nlist.upload(b->enc.img_nlist, st) || b->enc.d_scan_cost.alloc(b->enc.swork.size() + 1) || b->enc.d_slot_eobh.alloc(16 * size_t(b->enc.nslots) + 16) || b->enc.d_chunk_bits.alloc(size_t(b->enc.nslots) + 1) || b->enc.d_chunk_off.alloc(size_t(b->enc.nslots) + 2) || b->enc.d_tok_cursor.alloc(b->enc.region_est.size() + 1) || b->enc.d_regions.upload(b->enc.regions, st) ||
         b->enc.d_tables.alloc(b->enc.ntables) || b->enc.d_scan_pad.alloc(b->enc.swork.size() + 1) ||
-        b->enc.d_nzlists.upload(b->enc.nzlists, st) || b->enc.d_nzsets.upload(b->enc.nzsets, st) || b->enc.d_nzchunks.upload(b->enc.nzchunks, st) || (b->enc.n_fused && b->enc.d_nzchunks_fused.upload(b->enc.nzchunks_fused, st)) || b->enc.d_list_slots.alloc(size_t(b->enc.nlist_slots) + 1) || b->enc.d_tok_slots.alloc(size_t(b->enc.ntok_slots) + 1) || b->enc.d_ref_slots.alloc(size_t(b->enc.nref_slots) + 1) ||
+        b->enc.d_nzlists.upload(b->enc.nzlists, st) || b->enc.d_nzsets.upload(b->enc.nzsets, st) || b->enc.d_nzchunks.upload(b->enc.nzchunks, st) || (b->enc.n_fused && b->enc.d_nzchunks_fused.upload(b->enc.nzchunks_fused, st)) || b->enc.d_list_slots.alloc(size_t(b->enc.nlist_slots) + 1) || b->enc.d_tok_slots.alloc(size_t(b->enc.ntok_slots) + 1) || b->enc.d_ref_slots.alloc(size_t(b->enc.nref_slots) + 1) || b->enc.d_list_runs.alloc(size_t(b->enc.nlist_runs) + 1) || b->enc.d_ref_runs.alloc(size_t(b->enc.nref_runs) + 1) ||
         b->enc.d_nz_cursor.alloc(b->enc.nzlists.size() + 1) || b->enc.d_nz_chunk_off.alloc(size_t(b->enc.nz_nrec) + 1) || b->enc.d_nz_chunk_cnt.alloc(size_t(b->enc.nz_nrec) + 1) ||
         b->enc.d_scan_raw_off.alloc(b->enc.swork.size() + 2) || b->out.d_img_size.alloc(b->nimg + 1) || b->out.d_img_size_pad.alloc(b->nimg + 1) ||
         b->out.d_img_off.alloc(b->nimg + 2) || b->out.d_status.alloc(b->nimg) || b->out.d_overflow.alloc(4))
@@ -1179,7 +1185,7 @@ int BatchPlanner::upload(Laps &laps) {
     // the slots of every work item, written where they are used (the host counted them: add_works)
     if (hipMemsetAsync(b->enc.d_slots.p, 0, (size_t(b->enc.nslots) + 1) * sizeof(SlotRec), st) != hipSuccess ||
         hipMemsetAsync(b->enc.d_slot_work.p, 0, (size_t(b->enc.nslots) + 1) * sizeof(uint32_t), st) != hipSuccess) { csh_set_error("hipMemsetAsync failed"); return CS_ERR_NO_DEVICE; }
-    launch_make_slots(st, b->enc.d_swork.p, uint32_t(b->enc.swork.size()), b->enc.d_script.p, b->enc.d_nzlists.p, b->enc.d_slots.p, b->enc.d_slot_work.p, b->enc.d_list_slots.p, b->enc.d_tok_slots.p, b->enc.d_ref_slots.p);
+    launch_make_slots(st, b->enc.d_swork.p, uint32_t(b->enc.swork.size()), b->enc.d_script.p, b->enc.d_nzlists.p, b->enc.d_slots.p, b->enc.d_slot_work.p, b->enc.d_list_slots.p, b->enc.d_tok_slots.p, b->enc.d_ref_slots.p, b->enc.d_list_runs.p, b->enc.d_ref_runs.p, b->enc.list_run);
     if (b->tr.trellis && (b->tr.d_trows.upload(b->tr.trows, st) || (b->tr.t_sort && (b->tr.d_tperm.alloc(size_t(b->tr.t_units) + 1) || b->tr.d_tblk_cnt.alloc(size_t(b->tr.t_units) + 1) || (b->tr.nz_once && b->tr.d_tblk_off.alloc(size_t(b->tr.t_units) + 1)))))) return CS_ERR_NO_DEVICE;
     if (b->tr.trellis && (b->tr.d_twork.upload(b->tr.twork, st) || b->tr.d_truns.upload(b->tr.truns, st) || b->tr.d_tqueue.alloc(1) || b->tr.d_tlambda.alloc(size_t(b->tr.t_units) + 1) || b->tr.d_tdcbt.alloc(size_t(b->tr.t_units) + 1) ||
                        b->tr.d_tspill.alloc(trellis_spill_words(trellis_ac_slots())) || b->pix.d_dct_raw.alloc(size_t(b->ntiles_out) * CSH_TILE_I16)))

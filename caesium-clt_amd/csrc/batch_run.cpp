@@ -281,12 +281,21 @@ struct Run {
         return 0;
     }
 
+    // csh_timing.n_list_runs: the list and refinement runs of the stage's work items that are coded (a gated stage launches the runs of the others too: they do nothing)
+    void count_list_runs(const Stage &sg, bool gate) {
+        for (uint32_t wi = sg.work0; (sg.nlr || sg.nrr) && wi < sg.work0 + sg.nwork; wi++) {
+            const ScanWork &w = b->enc.swork[wi];
+            if ((w.lr_base != 0xFFFFFFFFu || w.rr_base != 0xFFFFFFFFu) && (!gate || b->enc.work_active[wi])) b->enc.last_run_list_runs += ((w.nunits + 255u) / 256u + b->enc.list_run - 1u) / b->enc.list_run;
+        }
+    }
+
     void set_stage(const Stage &sg) {
         c.echunks = b->enc.d_echunks.p + sg.ech0; c.nechunks = sg.nech; c.slot0 = sg.slot0; c.nslots = sg.nslots;
         c.nzchunks = (fused ? b->enc.d_nzchunks_fused.p : b->enc.d_nzchunks.p) + sg.nzc0; c.nnzchunks = sg.nnzc;
         c.nz_build = sg.nz_build[fused ? 1 : 0]; c.nz_filter = sg.nz_filter[fused ? 1 : 0];
         c.list_slots = b->enc.d_list_slots.p + sg.ls0; c.nlist_slots = sg.nls; c.tok_slots = b->enc.d_tok_slots.p + sg.ts0; c.ntok_slots = sg.nts;
         c.ref_slots = b->enc.d_ref_slots.p + sg.rs0; c.nref_slots = sg.nrs;
+        c.list_runs = b->enc.d_list_runs.p + sg.lr0; c.nlist_runs = sg.nlr; c.ref_runs = b->enc.d_ref_runs.p + sg.rr0; c.nref_runs = sg.nrr; c.list_run = b->enc.list_run;
     }
 
     // ---- mozjpeg's trellis quantiser (CSH_PROFILE=mozjpeg): per component a statistics scan over the scalar-quantised coefficients
@@ -308,6 +317,7 @@ struct Run {
         }
         launch_tokens(st, c);       // (sequential output: one-component sequential scans, histograms only)
         launch_list_stats(st, c);
+        count_list_runs(tg, false);
         launch_ac_runs(st, c);
         launch_gen_tables(st, b->enc.d_tables.p + tg.table0, int(tg.ntables));
         c.stats_only = 0;
@@ -337,6 +347,7 @@ struct Run {
         launch_list_refine(st, c);  // AC refinement scans, from the lists (timed with k_tokens, whose kind-0 chunks they were)
         for (uint32_t wi = sg.work0; sg.nrs && wi < sg.work0 + sg.nwork; wi++)
             if (b->enc.swork[wi].rs_base != 0xFFFFFFFFu && (!gate || b->enc.work_active[wi])) b->enc.last_run_refine++;
+        count_list_runs(sg, gate);
         launch_tokens(st, c);       // DC and sequential-mode scans (CSH_REF_LIST=0: the refinement scans too, from the tiles)
         SMARK(KS_TOKENS);
         launch_list_stats(st, c);   // AC first-pass scans
@@ -442,6 +453,7 @@ struct Run {
 
 int run_once(csh_batch *b, csh_timing *t, bool requant_only) {
     Run r(b, t);
+    b->enc.last_run_list_runs = 0;
     b->enc.last_run_fused = 0; b->enc.last_run_refine = 0; b->enc.last_run_ac_lists = 0;
     if (r.pools() || r.marks.start()) return -1;
     // a re-run at another quality (size targeting): from the retained DCT -- unless the batch derings: the overshoot mozjpeg's deringing allows

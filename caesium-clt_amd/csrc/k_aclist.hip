@@ -306,14 +306,20 @@ __device__ __forceinline__ static NzEvent nz_event(uint32_t e, uint32_t p, uint3
     return v;
 }
 struct ListSlot { const uint32_t *lst; uint32_t n; };
-__device__ __forceinline__ static ListSlot list_of_slot(const EncCtx &c, const SlotRec &r) {
-    // the slot record names its list and its chunk record (k_make_slots): three independent loads here, not a chain of four (work item -> list
-    // -> chunk record -> offset); the waves of these kernels are short, and what they wait for first is this
+// chunk record `rec` of the list whose region starts at entry `base` of the pool: two independent loads.  A slot record names its list and its chunk record
+// (k_make_slots), and the chunks of a work item stand in consecutive records: a wave that codes a run of chunks loads the slot record and the list's base once
+__device__ __forceinline__ static ListSlot list_chunk(const EncCtx &c, uint64_t base, uint32_t rec) {
     ListSlot s;
-    s.n = c.nz_chunk_cnt[r.nzrec];
-    s.lst = c.nz_pool + c.nzlists[r.nzlist].base + c.nz_chunk_off[r.nzrec];
+    s.n = c.nz_chunk_cnt[rec];
+    s.lst = c.nz_pool + base + c.nz_chunk_off[rec];
     return s;
 }
+// ---- LIST RUNS.  The three walkers below take ONE WAVE per run of up to EncCtx::list_run (CSH_LIST_RUN) consecutive chunks j0 .. j0 + n - 1 of one work item
+// (EncCtx::list_runs / ref_runs name every run's first slot; n = min(list_run, nch - j0)).  A run never leaves its scan, so the slot record of its first chunk
+// stands for all of them -- band, tables, list, gate, placement -- and what differs follows from j: slot cs0 + i, chunk record nzrec + i, units unit0 + 256 i,
+// histogram rows hist_row + i ntables, correction words corr0 + 256 i.  Per run: the chain slot record -> list -> first entries, the LDS set-up, the atomics on
+// the scan's statistics; per chunk: what the later kernels read per slot, bit for bit what one wave per chunk wrote.  list_run = 1 is that mapping.
+__device__ __forceinline__ static uint32_t run_chunks(const EncCtx &c, const SlotRec &r) { const uint32_t left = r.nch - r.j; return left < c.list_run ? left : c.list_run; }
 // four consecutive entries per lane (the chunk starts on a 16-byte boundary and is padded to one with entries that code nothing)
 __device__ __forceinline__ static void list_load4(const ListSlot &s, uint32_t g, uint32_t &e0, uint32_t &e1, uint32_t &e2, uint32_t &e3) {
     uint4 q; q.x = q.y = q.z = q.w = 0u;
@@ -321,70 +327,116 @@ __device__ __forceinline__ static void list_load4(const ListSlot &s, uint32_t g,
     e0 = q.x; e1 = q.y; e2 = q.z; e3 = q.w;
 }
 
-// ---- statistics: ONE WAVE per (scan, chunk) slot.  Symbol histogram in LDS (four copies, lane & 3: the frequent symbols -- 0x01, 0x11,
-// 0x02 -- meet in most steps, and equal addresses serialise), raw-bit count, the has-symbol / ends-with-EOB bits of the chunk's 256 blocks.
+// a chunk's histogram out of the wave's four LDS copies: lane l takes symbols 4 l .. 4 l + 3 (one 16-byte read per copy), leaves the copies at zero for the next
+// chunk, writes the slot's row (one 8-byte store) and adds the counts to the run's sums
+__device__ __forceinline__ static void hist_flush(uint32_t *hist, uint16_t *row, LV<uint32_t> (&freq)[4]) {
+    LFOR(l) {
+        uint4 s; s.x = s.y = s.z = s.w = 0u;
+        CSH_UNROLL
+        for (int cpy = 0; cpy < 4; cpy++) {
+            uint4 *h = reinterpret_cast<uint4 *>(hist + 256 * cpy + 4 * l);
+            const uint4 v = *h;
+            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+            uint4 zero; zero.x = zero.y = zero.z = zero.w = 0u;
+            *h = zero;
+        }
+        uint2 o; o.x = (s.x & 0xFFFFu) | (s.y << 16); o.y = (s.z & 0xFFFFu) | (s.w << 16);
+        *reinterpret_cast<uint2 *>(row + 4 * l) = o;
+        freq[0][l] += s.x; freq[1][l] += s.y; freq[2][l] += s.z; freq[3][l] += s.w;
+    }
+}
+// the run's sums into the scan's symbol frequencies (integer sums: the order does not show)
+__device__ __forceinline__ static void freq_flush(uint32_t *dst, const LV<uint32_t> (&freq)[4]) {
+    LFOR(l) {
+        CSH_UNROLL
+        for (int q = 0; q < 4; q++) if (freq[q][l]) atomicAdd(&dst[4 * l + q], freq[q][l]);
+    }
+}
+// ---- statistics: ONE WAVE per run of (scan, chunk) slots.  Symbol histogram in LDS (four copies, lane & 3: the frequent symbols -- 0x01, 0x11,
+// 0x02 -- meet in most steps, and equal addresses serialise), raw-bit count, the has-symbol / ends-with-EOB bits of the chunk's 256 blocks: written per
+// slot.  The scan's symbol frequencies (tables[].freq) take the sums of the whole run, from four registers per lane, behind its last chunk.
 __global__ void __launch_bounds__(256) k_list_stats(EncCtx c) {
-    CSH_SHARED uint32_t s_hist[4][4][256];
+    CSH_SHARED alignas(16) uint32_t s_hist[4][4][256];
     CSH_SHARED uint32_t s_flag[4][16];    // words 0..7: has-symbol, 8..15: ends-with-EOB
-    const int wv = lwave();
+    const int wv = int(uni(uint32_t(lwave())));   // (said to be wave-uniform: the run's records are then scalar loads into SGPRs, not a copy per lane in VGPRs)
     const uint32_t idx = blockIdx.x * 4u + uint32_t(wv);
-    if (idx >= c.nlist_slots) return;
-    const uint32_t cs = c.list_slots[idx];
-    const SlotRec r = c.slots[cs];
+    if (idx >= c.nlist_runs) return;
+    const uint32_t cs0 = c.list_runs[idx];
+    const SlotRec r = c.slots[cs0];
     if (c.work_active && !c.work_active[r.work]) return;
-    const ListSlot ls = list_of_slot(c, r);
+    const uint32_t nrun = run_chunks(c, r);
+    const uint64_t lbase = c.nzlists[r.nzlist].base;
+    ListSlot nx = list_chunk(c, lbase, r.nzrec);
     uint32_t *hist = &s_hist[wv][0][0], *flag = s_flag[wv];
-    LFOR(l) { for (int i = l; i < 1024; i += 64) hist[i] = 0u; if (l < 16) flag[l] = 0u; }
+    LFOR(l) {   // (a chunk's flush leaves them at zero for the next)
+        uint4 zero; zero.x = zero.y = zero.z = zero.w = 0u;
+        for (int i = 4 * l; i < 1024; i += 256) *reinterpret_cast<uint4 *>(hist + i) = zero;
+        if (l < 16) flag[l] = 0u;
+    }
     CSP_WAVE_SYNC();
     const uint32_t Ss = r.Ss, Se = r.Se;
-    uint32_t carry = CSH_NZ_END;
-    LV<uint32_t> raw;
-    LFOR(l) raw[l] = 0u;
-    // (the next step's entries are asked for before this step's are looked at: a step is short, and what it waited for was its own load)
+    LV<uint32_t> freq[4];   // the run's count of symbols 4 l .. 4 l + 3
+    LFOR(l) { freq[0][l] = 0u; freq[1][l] = 0u; freq[2][l] = 0u; freq[3][l] = 0u; }
+    // (the next step's entries are asked for before this step's are looked at: a step is short, and what it waited for was its own load; behind a chunk's
+    // last step they are the next chunk's first, whose record was asked for when this chunk began)
     LV<uint32_t> x0, x1, x2, x3;
-    LFOR(l) list_load4(ls, 4u * uint32_t(l), x0[l], x1[l], x2[l], x3[l]);
-    for (uint32_t g0 = 0; g0 < ls.n; g0 += 256) {
-        const LV<uint32_t> e0 = x0, e1 = x1, e2 = x2, e3 = x3;
-        if (g0 + 256u < ls.n) LFOR(l) list_load4(ls, g0 + 256u + 4u * uint32_t(l), x0[l], x1[l], x2[l], x3[l]);
-        const LV<uint32_t> p0 = lprev(e3, carry);
-        carry = llast(e3);
-        LFOR(l) {
-            uint32_t *h = hist + 256 * (l & 3);
-            const uint32_t e[4] = {e0[l], e1[l], e2[l], e3[l]}, p[4] = {p0[l], e0[l], e1[l], e2[l]};
-            CSH_UNROLL
-            for (int q = 0; q < 4; q++) {
-                const NzEvent v = nz_event(e[q], p[q], Ss, Se);
-                if (v.coded) {
-                    atomicAdd(&h[((v.run & 15u) << 4) | v.size], 1u);
-                    if (v.run >> 4) atomicAdd(&h[0xF0], v.run >> 4);
-                    raw[l] += v.size;
-                } else if (v.term) {
-                    if (v.has) atomicOr(&flag[v.blk >> 5], 1u << (v.blk & 31u));
-                    if (v.eob) atomicOr(&flag[8u + (v.blk >> 5)], 1u << (v.blk & 31u));
+    bool ahead = false;
+    for (uint32_t ci = 0; ci < nrun; ci++) {
+        const ListSlot ls = nx;
+        const bool more = ci + 1u < nrun;
+        if (more) nx = list_chunk(c, lbase, r.nzrec + ci + 1u);
+        if (!ahead) LFOR(l) list_load4(ls, 4u * uint32_t(l), x0[l], x1[l], x2[l], x3[l]);
+        ahead = false;
+        uint32_t carry = CSH_NZ_END;
+        LV<uint32_t> raw;
+        LFOR(l) raw[l] = 0u;
+        for (uint32_t g0 = 0; g0 < ls.n; g0 += 256) {
+            const LV<uint32_t> e0 = x0, e1 = x1, e2 = x2, e3 = x3;
+            if (g0 + 256u < ls.n) LFOR(l) list_load4(ls, g0 + 256u + 4u * uint32_t(l), x0[l], x1[l], x2[l], x3[l]);
+            else if (more) { LFOR(l) list_load4(nx, 4u * uint32_t(l), x0[l], x1[l], x2[l], x3[l]); ahead = true; }
+            const LV<uint32_t> p0 = lprev(e3, carry);
+            carry = llast(e3);
+            LFOR(l) {
+                uint32_t *h = hist + 256 * (l & 3);
+                const uint32_t e[4] = {e0[l], e1[l], e2[l], e3[l]}, p[4] = {p0[l], e0[l], e1[l], e2[l]};
+                CSH_UNROLL
+                for (int q = 0; q < 4; q++) {
+                    const NzEvent v = nz_event(e[q], p[q], Ss, Se);
+                    if (v.coded) {
+                        atomicAdd(&h[((v.run & 15u) << 4) | v.size], 1u);
+                        if (v.run >> 4) atomicAdd(&h[0xF0], v.run >> 4);
+                        raw[l] += v.size;
+                    } else if (v.term) {
+                        if (v.has) atomicOr(&flag[v.blk >> 5], 1u << (v.blk & 31u));
+                        if (v.eob) atomicOr(&flag[8u + (v.blk >> 5)], 1u << (v.blk & 31u));
+                    }
                 }
             }
         }
-    }
-    CSP_WAVE_SYNC();
-    const uint32_t rawbits = lsum32(raw);
-    LFOR(l) {
-        for (int i = l; i < 256; i += 64) {
-            const uint32_t v = hist[i] + hist[256 + i] + hist[512 + i] + hist[768 + i];
-            c.slot_hist[size_t(r.hist_row) * 256u + uint32_t(i)] = uint16_t(v);
-            if (v) atomicAdd(&c.tables[r.table_base].freq[i], v);
+        CSP_WAVE_SYNC();
+        const uint32_t rawbits = lsum32(raw);
+        const uint32_t cs = cs0 + ci, j = r.j + ci, hist_row = r.hist_row + ci * uint32_t(r.ntables);
+        hist_flush(hist, c.slot_hist + size_t(hist_row) * 256u, freq);
+        LFOR(l) {
+            if (l == 0) c.slot_raw[cs] = rawbits;
+            if (l < 4 && j * 4u + uint32_t(l) < ((r.nunits_work + 63u) >> 6)) {   // lane = block bit, so the chunk's flags ARE four words of the scan's bit vectors
+                c.sym_bits[r.word_base + j * 4u + uint32_t(l)] = uint64_t(flag[2 * l]) | (uint64_t(flag[2 * l + 1]) << 32);
+                c.eob_bits[r.word_base + j * 4u + uint32_t(l)] = uint64_t(flag[8 + 2 * l]) | (uint64_t(flag[9 + 2 * l]) << 32);
+            }
         }
-        if (l == 0) c.slot_raw[cs] = rawbits;
-        if (l < 4 && r.j * 4u + uint32_t(l) < ((r.nunits_work + 63u) >> 6)) {   // lane = block bit, so the chunk's flags ARE four words of the scan's bit vectors
-            c.sym_bits[r.word_base + r.j * 4u + uint32_t(l)] = uint64_t(flag[2 * l]) | (uint64_t(flag[2 * l + 1]) << 32);
-            c.eob_bits[r.word_base + r.j * 4u + uint32_t(l)] = uint64_t(flag[8 + 2 * l]) | (uint64_t(flag[9 + 2 * l]) << 32);
-        }
+        CSP_WAVE_SYNC();
+        LFOR(l) if (l < 16) flag[l] = 0u;
+        CSP_WAVE_SYNC();
     }
+    freq_flush(c.tables[r.table_base].freq, freq);
 }
 
-// ---- pack: ONE WAVE per (scan, chunk) slot.  256 entries a step, four per lane: their bits (ZRLs, symbol + value bits; a block's EOBRUN
+// ---- pack: ONE WAVE per run of (scan, chunk) slots.  256 entries a step, four per lane: their bits (ZRLs, symbol + value bits; a block's EOBRUN
 // symbol at its end), a wave scan of the lengths, every lane ORs its pieces into the wave's LDS window of the bit stream.  The window is
-// word-aligned with the raw pool, so flushing it is a plain copy: only the chunk's first and last word can be shared with a neighbouring
-// chunk and are ORed in (k_zero_edges cleared them).
+// word-aligned with the raw pool, so flushing it is a plain copy.  Chunk j + 1 of a scan starts at the bit where chunk j ended (chunk_off is an exclusive
+// scan in slot order), so across the chunks of a run the position, the window and the code table simply carry on: only the RUN's first and last word can
+// be shared with a neighbouring run and are ORed in (k_zero_edges cleared them, with every chunk's); the words at the chunk edges inside the run are
+// plain stores by the wave that owns both sides of them.
 __device__ __forceinline__ static void lor_bits(uint32_t *words, uint64_t pos, uint32_t v, uint32_t n) {   // n in 1..32, at bit `pos` of a big-endian-logical word array
     v &= n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u);
     const uint64_t t = uint64_t(v) << (64u - n - uint32_t(pos & 31u));
@@ -393,102 +445,129 @@ __device__ __forceinline__ static void lor_bits(uint32_t *words, uint64_t pos, u
     if (lo) atomicOr(words + (pos >> 5) + 1, lo);
 }
 __global__ void __launch_bounds__(256) k_list_pack(EncCtx c) {
-    CSH_SHARED uint32_t s_win[4][CSH_LP_WORDS];
+    CSH_SHARED alignas(16) uint32_t s_win[4][CSH_LP_WORDS];
     CSH_SHARED uint32_t s_lut[4][256];
     CSH_SHARED uint16_t s_eob[4][256];
-    const int wv = lwave();
+    const int wv = int(uni(uint32_t(lwave())));   // (said to be wave-uniform: the run's records are then scalar loads into SGPRs, not a copy per lane in VGPRs)
     const uint32_t idx = blockIdx.x * 4u + uint32_t(wv);
-    if (idx >= c.nlist_slots) return;
-    const uint32_t cs = c.list_slots[idx];
-    const SlotRec r = c.slots[cs];
+    if (idx >= c.nlist_runs) return;
+    const uint32_t cs0 = c.list_runs[idx];
+    const SlotRec r = c.slots[cs0];
     if (c.work_active && !c.work_active[r.work]) return;
     const ScanWork &w = c.work[r.work];
     if (w.no_room) { LFOR(l) if (l == 0) c.status[w.image] = 20200; return; }   // decided per scan by k_scan_place
-    const ListSlot ls = list_of_slot(c, r);
-    // the chunk's place: bits [raw_bit0, raw_bit0 + nbits) of the raw pool; the scan's last chunk also carries the 1-bits that fill the last byte
+    const uint32_t nrun = run_chunks(c, r);
+    const uint64_t lbase = c.nzlists[r.nzlist].base;
+    ListSlot nx = list_chunk(c, lbase, r.nzrec);
+    // the run's place: from bit raw_bit0 of the raw pool on; the scan's last chunk (the last of its run) also carries the 1-bits that fill the last byte
     const uint64_t scan0 = c.chunk_off[r.first_chunk];
-    const uint64_t raw_bit0 = w.raw_off * 8 + (c.chunk_off[cs] - scan0);
+    const uint64_t raw_bit0 = w.raw_off * 8 + (c.chunk_off[cs0] - scan0);
     uint32_t pad = 0;
-    if (r.j == r.nch - 1) { const uint64_t total = c.chunk_off[r.first_chunk + r.nch] - scan0; pad = uint32_t((8 - (total & 7)) & 7); }
+    if (r.j + nrun == r.nch) { const uint64_t total = c.chunk_off[r.first_chunk + r.nch] - scan0; pad = uint32_t((8 - (total & 7)) & 7); }
     uint32_t *buf = s_win[wv], *lut = s_lut[wv];
     uint16_t *eobrun = s_eob[wv];
     LFOR(l) {
-        for (int i = l; i < 256; i += 64) {
-            lut[i] = c.tables[r.table_base].lut[i];
-            eobrun[i] = uint32_t(i) < r.nun ? c.eobrun[r.unit0 + uint32_t(i)] : uint16_t(0);
-        }
-        for (int i = l; i < CSH_LP_WORDS; i += 64) buf[i] = 0u;
+        for (int i = l; i < 256; i += 64) lut[i] = c.tables[r.table_base].lut[i];
+        uint4 zero; zero.x = zero.y = zero.z = zero.w = 0u;
+        for (int i = 4 * l; i < CSH_LP_WORDS; i += 256) *reinterpret_cast<uint4 *>(buf + i) = zero;
     }
     CSP_WAVE_SYNC();
     uint32_t *out = c.raw + (raw_bit0 >> 5);        // word 0 of the frame below
-    uint64_t pos = raw_bit0 & 31u;                   // next bit, in the frame whose word 0 is the chunk's first word in the pool
+    uint64_t pos = raw_bit0 & 31u;                   // next bit, in the frame whose word 0 is the run's first word in the pool
     uint32_t ww = 0;                                 // first word of the window
     bool first_flush = true;
     const uint32_t Ss = r.Ss, Se = r.Se;
     const uint32_t zrl = lut[0xF0], zc = zrl & 0xFFFFu, zl = zrl >> 16;
-    uint32_t carry = CSH_NZ_END;
-    const uint32_t n_ext = ls.n + (pad ? 1u : 0u);   // the byte fill rides as one more entry
-    LV<uint32_t> x0, x1, x2, x3;   // the next step's entries, asked for a step ahead
-    LFOR(l) list_load4(ls, 4u * uint32_t(l), x0[l], x1[l], x2[l], x3[l]);
-    for (uint32_t g0 = 0; g0 < n_ext; g0 += 256) {
-        const LV<uint32_t> e0 = x0, e1 = x1, e2 = x2, e3 = x3;
-        if (g0 + 256u < n_ext) LFOR(l) list_load4(ls, g0 + 256u + 4u * uint32_t(l), x0[l], x1[l], x2[l], x3[l]);
-        const LV<uint32_t> p0 = lprev(e3, carry);
-        carry = llast(e3);
-        // what every entry emits: nz[q] ZRLs, then the n[q] low bits of v[q]
-        LV<uint32_t> v0, v1, v2, v3, n0, n1, n2, n3, z, len;
-        LFOR(l) {
-            const uint32_t e[4] = {e0[l], e1[l], e2[l], e3[l]}, p[4] = {p0[l], e0[l], e1[l], e2[l]};
-            uint32_t v[4], n[4], zz = 0, ln = 0;
-            CSH_UNROLL
-            for (int q = 0; q < 4; q++) {
-                v[q] = 0; n[q] = 0;
-                const uint32_t g = g0 + 4u * uint32_t(l) + uint32_t(q);
-                const NzEvent ev = nz_event(e[q], p[q], Ss, Se);
-                if (g >= ls.n) { if (pad && g == ls.n) { v[q] = (1u << pad) - 1u; n[q] = pad; } }
-                else if (ev.coded) {
-                    const uint32_t t = lut[((ev.run & 15u) << 4) | ev.size];
-                    v[q] = ((t & 0xFFFFu) << ev.size) | ev.bits; n[q] = (t >> 16) + ev.size;   // <= 16 + 15 bits
-                    zz |= (ev.run >> 4) << (2 * q);
-                    ln += (ev.run >> 4) * zl;
-                } else if (ev.term) {
-                    const uint32_t run = eobrun[ev.blk];
-                    if (run) {
-                        const uint32_t nb = lbitlen(run) - 1u, t = lut[nb << 4];
-                        v[q] = ((t & 0xFFFFu) << nb) | (run & ((1u << nb) - 1u)); n[q] = (t >> 16) + nb;   // <= 16 + 14 bits
+    LV<uint32_t> x0, x1, x2, x3;   // the next step's entries, asked for a step ahead (behind a chunk's last step: the next chunk's first)
+    bool ahead = false;
+    for (uint32_t ci = 0; ci < nrun; ci++) {
+        const ListSlot ls = nx;
+        const bool more = ci + 1u < nrun;
+        if (more) nx = list_chunk(c, lbase, r.nzrec + ci + 1u);
+#ifdef CSH_EMUL
+        {   // (where a pool had no room the pass is repeated and its sizes are not of these lists: even then a run never gets ahead of its sized place -- DESIGN 4.1)
+            const uint64_t want = (raw_bit0 & 31u) + (c.chunk_off[cs0 + ci] - c.chunk_off[cs0]);
+            if (c.overflow[1] ? pos > want : pos != want) { fprintf(stderr, "k_list_pack: chunk %u of a run does not start where the one before it ended\n", ci); abort(); }
+        }
+#endif
+        CSP_WAVE_SYNC();   // (the steps of the chunk before have read their EOBRUN values)
+        {
+            const uint32_t u0 = r.unit0 + 256u * ci, left = r.nunits_work - 256u * (r.j + ci), nun = left < 256u ? left : 256u;
+            LFOR(l) for (int i = l; i < 256; i += 64) eobrun[i] = uint32_t(i) < nun ? c.eobrun[u0 + uint32_t(i)] : uint16_t(0);
+        }
+        CSP_WAVE_SYNC();
+        if (!ahead) LFOR(l) list_load4(ls, 4u * uint32_t(l), x0[l], x1[l], x2[l], x3[l]);
+        ahead = false;
+        uint32_t carry = CSH_NZ_END;
+        const uint32_t cpad = more ? 0u : pad;
+        const uint32_t n_ext = ls.n + (cpad ? 1u : 0u);   // the byte fill rides as one more entry
+        for (uint32_t g0 = 0; g0 < n_ext; g0 += 256) {
+            const LV<uint32_t> e0 = x0, e1 = x1, e2 = x2, e3 = x3;
+            if (g0 + 256u < n_ext) LFOR(l) list_load4(ls, g0 + 256u + 4u * uint32_t(l), x0[l], x1[l], x2[l], x3[l]);
+            else if (more) { LFOR(l) list_load4(nx, 4u * uint32_t(l), x0[l], x1[l], x2[l], x3[l]); ahead = true; }
+            const LV<uint32_t> p0 = lprev(e3, carry);
+            carry = llast(e3);
+            // what every entry emits: nz[q] ZRLs, then the n[q] low bits of v[q]
+            LV<uint32_t> v0, v1, v2, v3, n0, n1, n2, n3, z, len;
+            LFOR(l) {
+                const uint32_t e[4] = {e0[l], e1[l], e2[l], e3[l]}, p[4] = {p0[l], e0[l], e1[l], e2[l]};
+                uint32_t v[4], n[4], zz = 0, ln = 0;
+                CSH_UNROLL
+                for (int q = 0; q < 4; q++) {
+                    v[q] = 0; n[q] = 0;
+                    const uint32_t g = g0 + 4u * uint32_t(l) + uint32_t(q);
+                    const NzEvent ev = nz_event(e[q], p[q], Ss, Se);
+                    if (g >= ls.n) { if (cpad && g == ls.n) { v[q] = (1u << cpad) - 1u; n[q] = cpad; } }
+                    else if (ev.coded) {
+                        const uint32_t t = lut[((ev.run & 15u) << 4) | ev.size];
+                        v[q] = ((t & 0xFFFFu) << ev.size) | ev.bits; n[q] = (t >> 16) + ev.size;   // <= 16 + 15 bits
+                        zz |= (ev.run >> 4) << (2 * q);
+                        ln += (ev.run >> 4) * zl;
+                    } else if (ev.term) {
+                        const uint32_t run = eobrun[ev.blk];
+                        if (run) {
+                            const uint32_t nb = lbitlen(run) - 1u, t = lut[nb << 4];
+                            v[q] = ((t & 0xFFFFu) << nb) | (run & ((1u << nb) - 1u)); n[q] = (t >> 16) + nb;   // <= 16 + 14 bits
+                        }
                     }
+                    ln += n[q];
                 }
-                ln += n[q];
+                v0[l] = v[0]; v1[l] = v[1]; v2[l] = v[2]; v3[l] = v[3]; n0[l] = n[0]; n1[l] = n[1]; n2[l] = n[2]; n3[l] = n[3]; z[l] = zz; len[l] = ln;
             }
-            v0[l] = v[0]; v1[l] = v[1]; v2[l] = v[2]; v3[l] = v[3]; n0[l] = n[0]; n1[l] = n[1]; n2[l] = n[2]; n3[l] = n[3]; z[l] = zz; len[l] = ln;
-        }
-        uint32_t tot;
-        const LV<uint32_t> ex = lscan(len, tot);
-        LFOR(l) {
-            uint64_t at = pos + ex[l] - uint64_t(ww) * 32u;    // bit position inside the window
-            const uint32_t v[4] = {v0[l], v1[l], v2[l], v3[l]}, n[4] = {n0[l], n1[l], n2[l], n3[l]};
-            CSH_UNROLL
-            for (int q = 0; q < 4; q++) {
-                for (uint32_t t = (z[l] >> (2 * q)) & 3u; t; t--) { lor_bits(buf, at, zc, zl); at += zl; }
-                if (n[q]) { lor_bits(buf, at, v[q], n[q]); at += n[q]; }
+            uint32_t tot;
+            const LV<uint32_t> ex = lscan(len, tot);
+            LFOR(l) {
+                uint64_t at = pos + ex[l] - uint64_t(ww) * 32u;    // bit position inside the window
+                const uint32_t v[4] = {v0[l], v1[l], v2[l], v3[l]}, n[4] = {n0[l], n1[l], n2[l], n3[l]};
+                CSH_UNROLL
+                for (int q = 0; q < 4; q++) {
+                    for (uint32_t t = (z[l] >> (2 * q)) & 3u; t; t--) { lor_bits(buf, at, zc, zl); at += zl; }
+                    if (n[q]) { lor_bits(buf, at, v[q], n[q]); at += n[q]; }
+                }
             }
-        }
-        pos += tot;
-        // slide the window when another step's worth of bits might not fit any more
-        const uint32_t done = uint32_t(pos >> 5) - ww;   // complete words in the window
-        if (done > CSH_LP_WORDS - 640) {
-            CSP_WAVE_SYNC();
-            LFOR(l) for (uint32_t q = uint32_t(l); q < done; q += 64) {
-                const uint32_t v = buf[q];
-                if (first_flush && q == 0) { if (v) atomicOr(out + ww, v); } else out[ww + q] = v;
+            pos += tot;
+            // slide the window when another step's worth of bits might not fit any more
+            const uint32_t done = uint32_t(pos >> 5) - ww;   // complete words in the window
+            if (done > CSH_LP_WORDS - 640) {
+                CSP_WAVE_SYNC();
+                LFOR(l) for (uint32_t q = uint32_t(l); q < done; q += 64) {
+                    const uint32_t v = buf[q];
+                    if (first_flush && q == 0) { if (v) atomicOr(out + ww, v); } else out[ww + q] = v;
+                }
+                const uint32_t partial = buf[done];
+                CSP_WAVE_SYNC();
+                LFOR(l) for (int q = l; q < CSH_LP_WORDS; q += 64) buf[q] = (q == 0) ? partial : 0u;
+                CSP_WAVE_SYNC();
+                ww += done; first_flush = false;
             }
-            const uint32_t partial = buf[done];
-            CSP_WAVE_SYNC();
-            LFOR(l) for (int q = l; q < CSH_LP_WORDS; q += 64) buf[q] = (q == 0) ? partial : 0u;
-            CSP_WAVE_SYNC();
-            ww += done; first_flush = false;
         }
     }
+#ifdef CSH_EMUL
+    {
+        const uint64_t want = (raw_bit0 & 31u) + (c.chunk_off[cs0 + nrun] - c.chunk_off[cs0]) + pad;
+        if (c.overflow[1] ? pos > want : pos != want) { fprintf(stderr, "k_list_pack: a run does not end where its sizes say\n"); abort(); }
+    }
+#endif
     CSP_WAVE_SYNC();
     const uint32_t last = uint32_t((pos + 31) >> 5) - ww;   // words in the window that carry bits
     LFOR(l) for (uint32_t q = uint32_t(l); q < last; q += 64) {
@@ -501,7 +580,7 @@ __global__ void __launch_bounds__(256) k_list_pack(EncCtx c) {
 // A refinement scan is a flat walk over the component's level-Al list too: an entry of magnitude 1 (after >> Al) is a newly significant
 // coefficient (N), one of magnitude >= 2 a coefficient with history (H) whose bit 0 is its correction bit; no tile is read, no bit plane made,
 // and no lane walks a block by itself.  What k_tokens' kind-0 chunks made for such a scan (k_entropy.hip emit_ac_refine, refine_room,
-// correction_word: the specification) comes out of k_list_refine, ONE WAVE per (scan, chunk) slot, four entries per lane and step:
+// correction_word: the specification) comes out of k_list_refine, ONE WAVE per run of (scan, chunk) slots (LIST RUNS above), four entries per lane and step:
 //   per entry, segmented by the blocks' END entries and carried across the steps:
 //     hex   H entries of the block in front of it (its correction bit is bit 63 - hex of the block's correction word)
 //     z     zeros of the band in front of it:  k - Ss - (N and H entries of the block in front of it)
@@ -568,31 +647,44 @@ __device__ __forceinline__ static void ref_step(const LV<uint32_t> (&e)[4], uint
         }
     }
 }
-__global__ void __launch_bounds__(256) k_list_refine(EncCtx c) {
-    CSH_SHARED uint32_t s_hist[4][4][256];   // four copies, lane & 3 (k_list_stats)
+__global__ void __launch_bounds__(256, 5) k_list_refine(EncCtx c) {   // (five waves per SIMD: what its 32 KB of LDS per workgroup allow)
+    CSH_SHARED alignas(16) uint32_t s_hist[4][4][256];   // four copies, lane & 3 (k_list_stats)
     CSH_SHARED uint32_t s_lastn[4][256];     // per block: its last N, k << 6 | hex (0: no N)
     CSH_SHARED uint32_t s_nh[4][256];        // per block: its H entries
     CSH_SHARED uint32_t s_corr[4][256][2];   // per block: its correction word, high half first
-    const int wv = lwave();
+    const int wv = int(uni(uint32_t(lwave())));   // (said to be wave-uniform: the run's records are then scalar loads into SGPRs, not a copy per lane in VGPRs)
     const uint32_t idx = blockIdx.x * 4u + uint32_t(wv);
-    if (idx >= c.nref_slots) return;
-    const uint32_t cs = c.ref_slots[idx];
-    const SlotRec r = c.slots[cs];
+    if (idx >= c.nref_runs) return;
+    const uint32_t cs0 = c.ref_runs[idx];
+    const SlotRec r = c.slots[cs0];
     if (c.work_active && !c.work_active[r.work]) return;
-    const ListSlot ls = list_of_slot(c, r);
+    const uint32_t nrun = run_chunks(c, r);
+    const uint64_t lbase = c.nzlists[r.nzlist].base;
+    ListSlot nx = list_chunk(c, lbase, r.nzrec);
+    const TokRegion rg = c.regions[r.region];
     uint32_t *hist = &s_hist[wv][0][0], *lastn = s_lastn[wv], *nh = s_nh[wv], *corr = &s_corr[wv][0][0];
-    LFOR(l) {
-        for (int i = l; i < 1024; i += 64) hist[i] = 0u;
-        for (int i = l; i < 256; i += 64) { lastn[i] = 0u; nh[i] = 0u; corr[2 * i] = 0u; corr[2 * i + 1] = 0u; }
+    LFOR(l) {   // (a chunk's flush leaves it at zero for the next)
+        uint4 zero; zero.x = zero.y = zero.z = zero.w = 0u;
+        for (int i = 4 * l; i < 1024; i += 256) *reinterpret_cast<uint4 *>(hist + i) = zero;
     }
-    CSP_WAVE_SYNC();
     const uint32_t Ss = r.Ss, Se = r.Se;
-    // ---- pass 1
-    RefCarry C;
-    C.runH = C.runN = C.base = C.prevN = C.prevNZ = 0u;
-    LV<uint32_t> ntok;
-    LFOR(l) ntok[l] = 0u;
-    {
+    LV<uint32_t> freq[4];   // the run's count of symbols 4 l .. 4 l + 3 (k_list_stats)
+    LFOR(l) { freq[0][l] = 0u; freq[1][l] = 0u; freq[2][l] = 0u; freq[3][l] = 0u; }
+    for (uint32_t ci = 0; ci < nrun; ci++) {
+        // (the next chunk's record is asked for now; its entries are not -- pass 2 needs the registers they would wait in)
+        const ListSlot ls = nx;
+        if (ci + 1u < nrun) nx = list_chunk(c, lbase, r.nzrec + ci + 1u);
+        const uint32_t cs = cs0 + ci, j = r.j + ci, unit0 = r.unit0 + 256u * ci, corr0 = r.corr0 + 256u * ci, hist_row = r.hist_row + ci * uint32_t(r.ntables);
+        const uint32_t left = r.nunits_work - 256u * j, nun = left < 256u ? left : 256u;
+        CSP_WAVE_SYNC();   // (pass 2 of the chunk before has read lastn and nh)
+        LFOR(l) for (int i = l; i < 256; i += 64) { lastn[i] = 0u; nh[i] = 0u; corr[2 * i] = 0u; corr[2 * i + 1] = 0u; }
+        CSP_WAVE_SYNC();
+        // ---- pass 1
+        RefCarry C;
+        C.runH = C.runN = C.base = C.prevN = C.prevNZ = 0u;
+        LV<uint32_t> ntok;
+        LFOR(l) ntok[l] = 0u;
+        {
         LV<uint32_t> x[4];   // the next step's entries, asked for a step ahead
         LFOR(l) list_load4(ls, 4u * uint32_t(l), x[0][l], x[1][l], x[2][l], x[3][l]);
         for (uint32_t g0 = 0; g0 < ls.n; g0 += 256) {
@@ -618,101 +710,96 @@ __global__ void __launch_bounds__(256) k_list_refine(EncCtx c) {
                 }
             }
         }
-    }
-    CSP_WAVE_SYNC();
-    // the blocks' ends: EOB tokens, tails, correction words, flags (lane = block bit, so the chunk's flags ARE four words of the scan's bit vectors)
-    for (uint32_t w4 = 0; w4 < 4; w4++) {
-        LFOR(l) {
-            const uint32_t i = 64u * w4 + uint32_t(l);
-            if (i < r.nun) {
-                const uint32_t ln = lastn[i];
-                if (ls.n && (ln >> 6) != Se) ntok[l] += 1u;   // (no entries: the list had no room, the run is repeated)
-                c.tail[r.unit0 + i] = uint8_t(nh[i] - (ln & 63u));   // the H entries behind the last N; all of them if there is no N
-                c.corr[r.corr0 + i] = (uint64_t(corr[2u * i]) << 32) | corr[2u * i + 1u];
-            }
         }
-        const uint64_t ms = lballot([&](int j) { const uint32_t i = 64u * w4 + uint32_t(j); return i < r.nun && lastn[i] != 0u; });
-        const uint64_t me = lballot([&](int j) { const uint32_t i = 64u * w4 + uint32_t(j); return i < r.nun && (lastn[i] >> 6) != Se; });
-        LFOR(l) if (l == 0 && r.j * 4u + w4 < ((r.nunits_work + 63u) >> 6)) { c.sym_bits[r.word_base + r.j * 4u + w4] = ms; c.eob_bits[r.word_base + r.j * 4u + w4] = me; }
-    }
-    const uint32_t total = lsum32(ntok);
-    LFOR(l) {
-        for (int i = l; i < 256; i += 64) {
-            const uint32_t v = hist[i] + hist[256 + i] + hist[512 + i] + hist[768 + i];
-            c.slot_hist[size_t(r.hist_row) * 256u + uint32_t(i)] = uint16_t(v);
-            if (v) atomicAdd(&c.tables[r.table_base].freq[i], v);
-        }
-        if (l == 0) c.slot_raw[cs] = C.runN + C.runH;   // a sign bit per new coefficient, a correction bit per old one
-    }
-    if (c.stats_only) return;   // (nothing is written to the pool)
-    // ---- room in the pool: one atomic add on the region's cursor
-    const TokRegion rg = c.regions[r.region];
-    uint32_t rel = 0;
-    LFOR(l) if (l == 0) rel = atomicAdd(&c.tok_cursor[r.region], total);
-    rel = uni(rel);
-    const bool ok = uint64_t(rel) + total <= rg.cap;
-    LFOR(l) {
-        if (l < 4) { c.tok_off[cs * 4u + uint32_t(l)] = rg.base + rel; c.chunk_ntok[cs * 4u + uint32_t(l)] = (ok && l == 0) ? total : 0u; }
-        if (l == 0 && !ok) c.overflow[1] = 1;
-    }
-    if (!ok) return;
-    uint32_t *tk = c.tokens + rg.base + rel;
-    // (both passes derive the counts from the same entries, so pass 2 writes exactly `total` tokens: `o < total` below cannot fail -- it is there so that a
-    // disagreement could never store outside the reserved room; the emulation build stops on one instead of dropping tokens)
-    // ---- pass 2: the tokens
-    C.runH = C.runN = C.base = C.prevN = C.prevNZ = 0u;
-    uint32_t curc = 0, at = 0;
-    for (uint32_t g0 = 0; g0 < ls.n; g0 += 256) {
-        LV<uint32_t> e[4], hex[4], z[4], zp[4], zq[4], cur[4], nt;
-        LFOR(l) list_load4(ls, g0 + 4u * uint32_t(l), e[0][l], e[1][l], e[2][l], e[3][l]);
-        ref_step<true>(e, Ss, Se, C, hex, z, zp, zq);
-        // zq <- the entry's ZRLs | its tokens << 8;  cur: the key of an emitting entry
-        LFOR(l) {
-            uint32_t s = 0;
-            CSH_UNROLL
-            for (int q = 0; q < 4; q++) {
-                const uint32_t v = e[q][l], blk = (v >> 23) & 255u, lastk = lastn[blk] >> 6, isN = ref_isN(v, Ss, Se);
-                uint32_t nz = 0, n = 0;
-                if ((isN | ref_isH(v, Ss, Se)) && (v & 127u) <= lastk) { nz = ((z[q][l] - zp[q][l]) >> 4) - ((zq[q][l] - zp[q][l]) >> 4); n = nz + isN; }
-                cur[q][l] = n ? ((blk + 1u) << 6) | hex[q][l] : 0u;
-                if ((v & CSH_NZ_END) && lastk != Se) n = 1u;
-                zq[q][l] = nz | (n << 8);
-                s += n;
-            }
-            nt[l] = s;
-        }
-        lscan_last4(cur, curc);
-        uint32_t tot;
-        const LV<uint32_t> ex = lscan(nt, tot);
-        LFOR(l) {
-            uint32_t o = at + ex[l];
-            CSH_UNROLL
-            for (int q = 0; q < 4; q++) {
-                const uint32_t v = e[q][l], blk = (v >> 23) & 255u, nz = zq[q][l] & 255u, n = zq[q][l] >> 8;
-                if (!n) continue;
-                const uint32_t cu = ref_same(cur[q][l], blk);
-                if (v & CSH_NZ_END) {
-                    if (o < total) tk[o] = TK_EOB | (blk << 3) | ((nh[blk] - cu) << 16) | (cu << 22);
-                    o++;
-                    continue;
-                }
-                // the first token takes the correction bits since the block's last emitting entry, the others none
-                uint32_t cnt = hex[q][l] - cu, from = cu;
-                for (uint32_t t = 0; t < nz; t++) {
-                    if (o < total) tk[o] = TK_REF | (blk << 3) | (cnt << 16) | (from << 22) | (1u << 28);
-                    o++; cnt = 0u; from = hex[q][l];
-                }
-                if (n > nz) {
-                    if (o < total) tk[o] = TK_REF | (blk << 3) | (((z[q][l] - zp[q][l]) & 15u) << 11) | ((v & 128u) ? 0u : (1u << 15)) | (cnt << 16) | (from << 22);
-                    o++;
+        CSP_WAVE_SYNC();
+        // the blocks' ends: EOB tokens, tails, correction words, flags (lane = block bit, so the chunk's flags ARE four words of the scan's bit vectors)
+        for (uint32_t w4 = 0; w4 < 4; w4++) {
+            LFOR(l) {
+                const uint32_t i = 64u * w4 + uint32_t(l);
+                if (i < nun) {
+                    const uint32_t ln = lastn[i];
+                    if (ls.n && (ln >> 6) != Se) ntok[l] += 1u;   // (no entries: the list had no room, the run is repeated)
+                    c.tail[unit0 + i] = uint8_t(nh[i] - (ln & 63u));   // the H entries behind the last N; all of them if there is no N
+                    c.corr[corr0 + i] = (uint64_t(corr[2u * i]) << 32) | corr[2u * i + 1u];
                 }
             }
+            const uint64_t ms = lballot([&](int b) { const uint32_t i = 64u * w4 + uint32_t(b); return i < nun && lastn[i] != 0u; });
+            const uint64_t me = lballot([&](int b) { const uint32_t i = 64u * w4 + uint32_t(b); return i < nun && (lastn[i] >> 6) != Se; });
+            LFOR(l) if (l == 0 && j * 4u + w4 < ((r.nunits_work + 63u) >> 6)) { c.sym_bits[r.word_base + j * 4u + w4] = ms; c.eob_bits[r.word_base + j * 4u + w4] = me; }
         }
-        at += tot;
-    }
+        const uint32_t total = lsum32(ntok);
+        hist_flush(hist, c.slot_hist + size_t(hist_row) * 256u, freq);
+        LFOR(l) if (l == 0) c.slot_raw[cs] = C.runN + C.runH;   // a sign bit per new coefficient, a correction bit per old one
+        if (c.stats_only) continue;   // (nothing is written to the pool)
+        // ---- room in the pool: one atomic add on the region's cursor
+        uint32_t rel = 0;
+        LFOR(l) if (l == 0) rel = atomicAdd(&c.tok_cursor[r.region], total);
+        rel = uni(rel);
+        const bool ok = uint64_t(rel) + total <= rg.cap;
+        LFOR(l) {
+            if (l < 4) { c.tok_off[cs * 4u + uint32_t(l)] = rg.base + rel; c.chunk_ntok[cs * 4u + uint32_t(l)] = (ok && l == 0) ? total : 0u; }
+            if (l == 0 && !ok) c.overflow[1] = 1;
+        }
+        if (!ok) continue;
+        uint32_t *tk = c.tokens + rg.base + rel;
+        // (both passes derive the counts from the same entries, so pass 2 writes exactly `total` tokens: `o < total` below cannot fail -- it is there so that a
+        // disagreement could never store outside the reserved room; the emulation build stops on one instead of dropping tokens)
+        // ---- pass 2: the tokens
+        C.runH = C.runN = C.base = C.prevN = C.prevNZ = 0u;
+        uint32_t curc = 0, at = 0;
+        for (uint32_t g0 = 0; g0 < ls.n; g0 += 256) {
+            LV<uint32_t> e[4], hex[4], z[4], zp[4], zq[4], cur[4], nt;
+            LFOR(l) list_load4(ls, g0 + 4u * uint32_t(l), e[0][l], e[1][l], e[2][l], e[3][l]);
+            ref_step<true>(e, Ss, Se, C, hex, z, zp, zq);
+            // zq <- the entry's ZRLs | its tokens << 8;  cur: the key of an emitting entry
+            LFOR(l) {
+                uint32_t s = 0;
+                CSH_UNROLL
+                for (int q = 0; q < 4; q++) {
+                    const uint32_t v = e[q][l], blk = (v >> 23) & 255u, lastk = lastn[blk] >> 6, isN = ref_isN(v, Ss, Se);
+                    uint32_t nz = 0, n = 0;
+                    if ((isN | ref_isH(v, Ss, Se)) && (v & 127u) <= lastk) { nz = ((z[q][l] - zp[q][l]) >> 4) - ((zq[q][l] - zp[q][l]) >> 4); n = nz + isN; }
+                    cur[q][l] = n ? ((blk + 1u) << 6) | hex[q][l] : 0u;
+                    if ((v & CSH_NZ_END) && lastk != Se) n = 1u;
+                    zq[q][l] = nz | (n << 8);
+                    s += n;
+                }
+                nt[l] = s;
+            }
+            lscan_last4(cur, curc);
+            uint32_t tot;
+            const LV<uint32_t> ex = lscan(nt, tot);
+            LFOR(l) {
+                uint32_t o = at + ex[l];
+                CSH_UNROLL
+                for (int q = 0; q < 4; q++) {
+                    const uint32_t v = e[q][l], blk = (v >> 23) & 255u, nz = zq[q][l] & 255u, n = zq[q][l] >> 8;
+                    if (!n) continue;
+                    const uint32_t cu = ref_same(cur[q][l], blk);
+                    if (v & CSH_NZ_END) {
+                        if (o < total) tk[o] = TK_EOB | (blk << 3) | ((nh[blk] - cu) << 16) | (cu << 22);
+                        o++;
+                        continue;
+                    }
+                    // the first token takes the correction bits since the block's last emitting entry, the others none
+                    uint32_t cnt = hex[q][l] - cu, from = cu;
+                    for (uint32_t t = 0; t < nz; t++) {
+                        if (o < total) tk[o] = TK_REF | (blk << 3) | (cnt << 16) | (from << 22) | (1u << 28);
+                        o++; cnt = 0u; from = hex[q][l];
+                    }
+                    if (n > nz) {
+                        if (o < total) tk[o] = TK_REF | (blk << 3) | (((z[q][l] - zp[q][l]) & 15u) << 11) | ((v & 128u) ? 0u : (1u << 15)) | (cnt << 16) | (from << 22);
+                        o++;
+                    }
+                }
+            }
+            at += tot;
+        }
 #ifdef CSH_EMUL
-    if (at != total) { fprintf(stderr, "k_list_refine: pass 2 made %u tokens, pass 1 counted %u\n", at, total); abort(); }
+        if (at != total) { fprintf(stderr, "k_list_refine: pass 2 made %u tokens, pass 1 counted %u\n", at, total); abort(); }
 #endif
+    }
+    freq_flush(c.tables[r.table_base].freq, freq);
 }
 
 __global__ void k_reset_works(ScanWork *work, int nwork) {
@@ -726,14 +813,15 @@ void launch_nzlist(hipStream_t st, const EncCtx &c) {
     if (c.nz_build) CSH_LAUNCH_PHASED(k_nzlist, 3, dim3(c.nnzchunks), dim3(2 * CSP_WAVE_THREADS), st, c);
     if (c.nz_filter) CSH_LAUNCH(k_nzfilter, dim3(c.nnzchunks), dim3(CSP_WAVE_THREADS), st, c);
 }
-void launch_list_stats(hipStream_t st, const EncCtx &c) { if (c.nlist_slots) CSH_LAUNCH(k_list_stats, dim3((c.nlist_slots + 3) / 4), dim3(4 * CSP_WAVE_THREADS), st, c); }
-void launch_list_refine(hipStream_t st, const EncCtx &c) { if (c.nref_slots) CSH_LAUNCH(k_list_refine, dim3((c.nref_slots + 3) / 4), dim3(4 * CSP_WAVE_THREADS), st, c); }
-void launch_list_pack(hipStream_t st, const EncCtx &c) { if (c.nlist_slots) CSH_LAUNCH(k_list_pack, dim3((c.nlist_slots + 3) / 4), dim3(4 * CSP_WAVE_THREADS), st, c); }
+// one wave per list run, four runs per workgroup
+void launch_list_stats(hipStream_t st, const EncCtx &c) { if (c.nlist_runs) CSH_LAUNCH(k_list_stats, dim3((c.nlist_runs + 3) / 4), dim3(4 * CSP_WAVE_THREADS), st, c); }
+void launch_list_refine(hipStream_t st, const EncCtx &c) { if (c.nref_runs) CSH_LAUNCH(k_list_refine, dim3((c.nref_runs + 3) / 4), dim3(4 * CSP_WAVE_THREADS), st, c); }
+void launch_list_pack(hipStream_t st, const EncCtx &c) { if (c.nlist_runs) CSH_LAUNCH(k_list_pack, dim3((c.nlist_runs + 3) / 4), dim3(4 * CSP_WAVE_THREADS), st, c); }
 // ---- the slots of the work items: one workgroup per work item, one lane per 256-unit chunk.  Under the scan search a 1080p image has ~3.9 k slots in 58 work
 // items: built on the host they were 64 MB of records per 256 files to write and to upload in front of the first kernel (the boundary call paid ~15 ms of
 // every 50 for them); the host only counts them now (batch_plan.cpp add_works).  Slots between the stages belong to no work item and stay zero.
 __global__ void __launch_bounds__(64) k_make_slots(const ScanWork *works, uint32_t nworks, const EncScan *script, const NzList *nzlists, SlotRec *slots, uint32_t *slot_work, uint32_t *list_slots,
-                                                   uint32_t *tok_slots, uint32_t *ref_slots) {
+                                                   uint32_t *tok_slots, uint32_t *ref_slots, uint32_t *list_runs, uint32_t *ref_runs, uint32_t list_run) {
     const uint32_t wi = blockIdx.x;
     if (wi >= nworks) return;
     const ScanWork &w = works[wi];
@@ -755,6 +843,9 @@ __global__ void __launch_bounds__(64) k_make_slots(const ScanWork *works, uint32
         slot_work[w.first_chunk + j] = wi;
         (listed ? list_slots : tok_slots)[w.ls_base + j] = w.first_chunk + j;
         if (ref_list) ref_slots[w.rs_base + j] = w.first_chunk + j;
+        // the list runs (k_list_stats, k_list_pack / k_list_refine): the first slot of every run of list_run chunks; the last run of a work item is as long as what is left
+        if (listed && j % list_run == 0u) list_runs[w.lr_base + j / list_run] = w.first_chunk + j;
+        if (ref_list && j % list_run == 0u) ref_runs[w.rr_base + j / list_run] = w.first_chunk + j;
     }
 }
 // the scan search re-points work items to the lists of the point transform it chose (scan_search.cpp search_decide): their slots follow
@@ -770,9 +861,9 @@ void launch_rebind_slots(hipStream_t st, const ScanWork *works, uint32_t nworks,
     if (nworks) CSH_LAUNCH(k_rebind_slots, dim3(nworks), dim3(64), st, works, nworks, nzlists, slots);
 }
 void launch_make_slots(hipStream_t st, const ScanWork *works, uint32_t nworks, const EncScan *script, const NzList *nzlists, SlotRec *slots, uint32_t *slot_work, uint32_t *list_slots,
-                       uint32_t *tok_slots, uint32_t *ref_slots) {
+                       uint32_t *tok_slots, uint32_t *ref_slots, uint32_t *list_runs, uint32_t *ref_runs, uint32_t list_run) {
     if (!nworks) return;
-    CSH_LAUNCH(k_make_slots, dim3(nworks), dim3(64), st, works, nworks, script, nzlists, slots, slot_work, list_slots, tok_slots, ref_slots);
+    CSH_LAUNCH(k_make_slots, dim3(nworks), dim3(64), st, works, nworks, script, nzlists, slots, slot_work, list_slots, tok_slots, ref_slots, list_runs, ref_runs, list_run);
 }
 
 void launch_reset_works(hipStream_t st, ScanWork *work, int nwork) { if (nwork) CSH_LAUNCH(k_reset_works, dim3((nwork + 255) / 256), dim3(256), st, work, nwork); }

@@ -73,7 +73,7 @@ void launch_refine_chains(hipStream_t st, const uint8_t *clean, const ParScan *p
 // per (work item, 256-unit chunk): SlotRec, slot -> work item, and the slot's entry in the list-coded / token-coded slot lists (k_aclist.hip)
 void launch_rebind_slots(hipStream_t st, const ScanWork *works, uint32_t nworks, const NzList *nzlists, SlotRec *slots);   // after the host re-points work items' lists
 void launch_make_slots(hipStream_t st, const ScanWork *works, uint32_t nworks, const EncScan *script, const NzList *nzlists, SlotRec *slots, uint32_t *slot_work, uint32_t *list_slots,
-                       uint32_t *tok_slots, uint32_t *ref_slots);
+                       uint32_t *tok_slots, uint32_t *ref_slots, uint32_t *list_runs, uint32_t *ref_runs, uint32_t list_run);   // list_runs / ref_runs: the first slot of every run of list_run chunks (ScanWork::lr_base / rr_base)
 void launch_decode_prog(hipStream_t st, const uint8_t *clean, const ParScan *pss, const ParHuffSet *huffs, const DecScan *scans, const ProgChain *chains,
                         const int *chain_scans, int nchains, const ImgDesc *imgs, int16_t *coef, uint32_t *need_seq);
 void launch_dec_mark_pending(hipStream_t st, const ParScan *ps, uint32_t total_sub, const uint64_t *list_in, const uint32_t *cnt_in, uint32_t *scan_pending);
@@ -173,6 +173,13 @@ struct EncCtx {  // device pointers + sizes every entropy kernel needs
     uint32_t ntok_slots;
     const uint32_t *ref_slots; // those of the token-coded slots that are refinement scans coded from their list: k_list_refine writes their tokens (k_tokens does not)
     uint32_t nref_slots;
+    // the grids of k_list_stats, k_list_pack (list_runs) and k_list_refine (ref_runs): one wave per run of up to list_run consecutive chunks of a work item
+    // -- the first slot of every run; its length is min(list_run, chunks left in the work item).  list_run = 1: one wave per slot, list_runs == list_slots
+    const uint32_t *list_runs;
+    uint32_t nlist_runs;
+    const uint32_t *ref_runs;
+    uint32_t nref_runs;
+    uint32_t list_run;         // CSH_LIST_RUN, 1..32
     uint32_t nz_build, nz_filter; // the run's NzChunks: some asks for level 0 from the tiles (k_nzlist) / for a filtered level (k_nzfilter); a kernel nobody asks for is not launched
 };
 enum : uint32_t { TK_SYM = 0u, TK_RAW = 1u, TK_ACF = 2u, TK_REF = 3u, TK_EOB = 4u };   // token kinds (bits 0-2 of a token; the fields: k_entropy.hip)
@@ -198,6 +205,9 @@ void launch_reset_works(hipStream_t st, ScanWork *work, int nwork);
 
 // ---- mozjpeg's trellis quantiser (k_trellis.hip): re-quantise every block from the retained DCT with the statistics pass's code
 // lengths as rates -- AC coefficients per block (k_trellis_ac), DC coefficients along each row of blocks (k_trellis_dc)
+#ifndef CSH_LIST_RUN
+#define CSH_LIST_RUN 8  // chunks per list run at most, unless the environment's CSH_LIST_RUN (1..32) says otherwise (the sweep over 1, 2, 4, 8 and 16)
+#endif
 #ifndef CSH_TR_WG
 #define CSH_TR_WG 256   // blocks per workgroup (and per chunk) of k_trellis_ac (64 -- no wave waits for another's densest block, but the tables are staged four times as often -- measured 6 % slower)
 #endif

@@ -220,6 +220,8 @@ struct ScanWork {
     uint32_t ls_base;      // where its slots stand in the list of list-coded slots (first-pass scans with a list) or of token-coded slots
     uint32_t rs_base;      // refinement scans coded from their list (k_list_refine): where its slots stand in the list of such slots; 0xFFFFFFFF otherwise
     uint32_t region;       // ... and the region of the token pool their tokens go to (one per image, component and stage)
+    uint32_t lr_base;      // first-pass scans with a list: where its runs of CSH_LIST_RUN chunks stand in the list of list runs (EncCtx::list_runs)
+    uint32_t rr_base;      // refinement scans coded from their list: the same in EncCtx::ref_runs
 };
 
 // one workgroup of the token kernel (k_tokens): 256 consecutive units, [256 j, 256 j + 256)

@@ -140,6 +140,9 @@ typedef struct {
     uint32_t n_ac_in_lists;       /* components whose quantised AC levels this run did not store to the coefficient tiles: every coding kernel takes them from the coefficient
                                      lists.  0 with CSH_AC_TILES=1 (and with any of CSH_NZ_FUSED=0, CSH_NZ_ONCE=0, CSH_TR_SORT=0, CSH_REF_LIST=0), in a re-quantisation run, for
                                      sequential output, and for components counted out of n_fused_lists */
+    uint32_t n_list_runs;         /* waves' worth of work of the list kernels in this run: the runs of up to CSH_LIST_RUN (1..32) consecutive 256-block chunks that the progressive AC
+                                     work items this run coded from the coefficient lists were cut into -- the sum of ceil(chunks / CSH_LIST_RUN) over them, all stages (the trellis
+                                     quantiser's statistics scans and the scan search's candidates included).  0 for sequential output */
 } csh_timing;
 
 int csh_device_count(void);
