@@ -108,6 +108,7 @@ struct EncodePlan {
     // k_list_stats, k_list_pack and k_list_refine take one wave per run of up to list_run consecutive chunks of a work item: the runs are counted beside the slots
     uint32_t list_run = CSH_LIST_RUN;     // PlanSwitches::list_run
     uint32_t nlist_runs = 0, nref_runs = 0;
+    bool ac_runs_slot = false;            // PlanSwitches::ac_runs_slot
     uint32_t last_run_list_runs = 0;      // list and refinement runs of the work items the last run coded, all stages (csh_timing.n_list_runs)
     uint64_t total_corr = 0;              // correction words: one per unit of a refinement scan
     uint64_t total_units = 0, total_words = 0;
@@ -312,6 +313,7 @@ struct PlanSwitches {
     bool nz_fused = true;       // CSH_NZ_FUSED != "0": the forward-DCT kernels build the level-0 coefficient lists
     bool ref_list = true;       // CSH_REF_LIST != "0": the AC refinement scans are coded from the coefficient lists (k_list_refine), not from the tiles (k_tokens' kind-0 chunks)
     uint32_t list_run = CSH_LIST_RUN;   // CSH_LIST_RUN, clamped to 1..32: chunks per wave of k_list_stats, k_list_pack and k_list_refine (1: one wave per chunk)
+    bool ac_runs_slot = false;  // CSH_AC_RUNS == "slot": k_ac_runs takes one wave per slot, as before it took one per 16 slots (k_ac_runs_words)
     bool ac_tiles = false;      // CSH_AC_TILES == "1": every component's AC levels are stored to its tiles, as before they lived in the lists
     static PlanSwitches read();
 };

@@ -242,6 +242,7 @@ PlanSwitches PlanSwitches::read() {
     s.prog_par = pp && !strcmp(pp, "0") ? 0 : (pp && !strcmp(pp, "1") ? 1 : -1);
     s.fused_420 = !getenv("CSH_NO_FUSED_420");
     if (const char *lr = getenv("CSH_LIST_RUN")) { if (*lr) s.list_run = uint32_t(std::min(32, std::max(1, atoi(lr)))); }
+    s.ac_runs_slot = is("CSH_AC_RUNS", "slot");
     return s;
 }
 
@@ -267,6 +268,7 @@ void BatchPlanner::begin() {
     for (int q = 1; q <= 100; q++) { uint16_t tq[64]; quality_table(q, tq); DevQuant dq; make_quant(tq, dq); b->quants.push_back(dq); }
     b->progressive = progressive;
     b->enc.list_run = sw.list_run;
+    b->enc.ac_runs_slot = sw.ac_runs_slot;
 
     add_script(b->enc.script, 3, true);   // entries 0..9
     add_script(b->enc.script, 1, true);   // entries 10..15

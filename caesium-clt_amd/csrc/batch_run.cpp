@@ -296,6 +296,7 @@ struct Run {
         c.list_slots = b->enc.d_list_slots.p + sg.ls0; c.nlist_slots = sg.nls; c.tok_slots = b->enc.d_tok_slots.p + sg.ts0; c.ntok_slots = sg.nts;
         c.ref_slots = b->enc.d_ref_slots.p + sg.rs0; c.nref_slots = sg.nrs;
         c.list_runs = b->enc.d_list_runs.p + sg.lr0; c.nlist_runs = sg.nlr; c.ref_runs = b->enc.d_ref_runs.p + sg.rr0; c.nref_runs = sg.nrr; c.list_run = b->enc.list_run;
+        c.ac_runs_slot = b->enc.ac_runs_slot ? 1u : 0u;
     }
 
     // ---- mozjpeg's trellis quantiser (CSH_PROFILE=mozjpeg): per component a statistics scan over the scalar-quantised coefficients

@@ -563,6 +563,16 @@ __global__ void __launch_bounds__(256, 3) k_tokens(EncCtx c) {
 // A run [u .. t] is cut into sub-runs as jcphuff.c does: after 0x7FFF blocks, and (refinement) as soon as more than
 // MAX_CORR_BITS - DCTSIZE2 + 1 = 937 correction bits are pending.  Serial form (short runs, and the emulation build):
 // count(run, owner): called for every EOBRUN symbol, with the block that emits it
+#ifdef CSH_EMUL
+// test hook of the emulation build (pipeline.cpp csh_emul_ac_paths): which paths the EOB-run kernels took since the last look --
+// [0] ordinary runs  [1] runs k_ac_runs / k_ac_runs_words resolved with eob_run_serial, [2] of them in a refinement scan  [3] sub-runs cut by the 937-bit limit
+// [4] runs handed to k_ac_runs_long  [5] k_ac_runs_words: flushes of the frequency sums at a change of work item inside a wave
+// [6] k_ac_runs_words: waves that begin inside a work item  [7] sub-runs cut after 0x7FFF blocks
+uint32_t csh_emul_ac_paths[8];
+#define CSH_ACR_PATH(i) ((void)csh_emul_ac_paths[i]++)
+#else
+#define CSH_ACR_PATH(i) ((void)0)
+#endif
 template <class Count>
 __device__ static void eob_run_serial(const EncCtx &c, const ScanWork &w, const EncScan &sc, uint32_t u, uint32_t t, Count count) {
     uint16_t *er = c.eobrun + w.unit_base;
@@ -575,7 +585,7 @@ __device__ static void eob_run_serial(const EncCtx &c, const ScanWork &w, const 
     uint32_t cnt = 0, be = 0, s0 = u;
     auto step = [&](uint32_t j, uint32_t tail_bits) {
         cnt++; be += tail_bits;
-        if (cnt == 0x7FFF || be > 937) { er[s0] = uint16_t(cnt); count(cnt, s0); cnt = 0; be = 0; s0 = j + 1; }
+        if (cnt == 0x7FFF || be > 937) { CSH_ACR_PATH(cnt == 0x7FFF ? 7 : 3); er[s0] = uint16_t(cnt); count(cnt, s0); cnt = 0; be = 0; s0 = j + 1; }
     };
     uint32_t j = u;
     while (j <= t && (reinterpret_cast<uintptr_t>(tl + j) & 7)) { step(j, tl[j]); j++; }
@@ -643,16 +653,18 @@ __global__ void __launch_bounds__(256) k_ac_runs(EncCtx c) {
                 if (len <= 14u || (len < 0x7FFFu && r.Ah == 0)) {
                     c.eobrun[r.unit_base + u] = uint16_t(len);
                     my_nb = bitlen32(len) - 1;
+                    CSH_ACR_PATH(0);
                 } else {
                     ScanWork w; w.unit_base = r.unit_base; w.word_base = r.word_base; w.nunits = nunits; w.first_chunk = r.first_chunk; w.table_base = r.table_base;
                     EncScan sc; sc.Ss = r.Ss; sc.Se = r.Se; sc.Ah = r.Ah; sc.Al = r.Al;
                     uint32_t t;
-                    if (eob_run_end(sym, nunits, u, CSH_LONG_RUN_WORDS, t))
+                    if (eob_run_end(sym, nunits, u, CSH_LONG_RUN_WORDS, t)) {
+                        CSH_ACR_PATH(1); if (r.Ah) CSH_ACR_PATH(2);
                         eob_run_serial(c, w, sc, u, t, [&](uint32_t run, uint32_t owner) {   // a run cut into sub-runs, or a long one: counted one by one
                             const int nb = bitlen32(run) - 1;
                             atomicAdd(&freq[nb << 4], 1u); atomicAdd(&c.slot_eobh[size_t(r.first_chunk + (owner >> 8)) * 16u + uint32_t(nb)], 1u);   // the symbol belongs to the chunk of the block that emits it
                         });
-                    else { uint32_t e = atomicAdd(c.long_cnt, 1u); c.long_runs[2 * e] = r.work; c.long_runs[2 * e + 1] = u; }
+                    } else { CSH_ACR_PATH(4); uint32_t e = atomicAdd(c.long_cnt, 1u); c.long_runs[2 * e] = r.work; c.long_runs[2 * e + 1] = u; }
                 }
             }
         }
@@ -676,6 +688,108 @@ __global__ void __launch_bounds__(256) k_ac_runs(EncCtx c) {
 #ifndef CSH_EMUL
     if (mine && lane < 15) { atomicAdd(&freq[lane << 4], mine); atomicAdd(&c.slot_eobh[cs * 16u + uint32_t(lane)], mine); }
 #endif
+}
+// The same, one WAVE per 16 consecutive slots of the stage (64 words of the bit vectors, 4096 blocks): the default form; CSH_AC_RUNS=slot keeps
+// the one above.  Lane l belongs to slot cs0 + (l >> 2) and to word 4 j + (l & 3) of that slot's work item: it reads the slot's record and
+// its word's four values once (the slot form had all 64 lanes load the same words, behind the record, in a wave of its own per slot).  The
+// wave then walks its words; the word's values and record fields come from its lane (readlane: scalar registers) and lane b is block b of
+// the word, with the slot form's statements.  The 16 slots may belong to several work items: nothing is taken to hold for the whole wave.
+// The EOBn counts of the ordinary runs go to slot_eobh once per slot, and to the table's frequencies once per (wave, work item) -- in a
+// 1080p luma scan one add per class and 16 slots where the slot form made 16, on the few addresses every slot of the scan adds to.
+#define CSH_ACR_SLOTS 16u
+__global__ void __launch_bounds__(256) k_ac_runs_words(EncCtx c) {
+    const uint32_t cs0 = c.slot0 + (blockIdx.x * 4u + uni(uint32_t(threadIdx.x) / CSP_WAVE_THREADS)) * CSH_ACR_SLOTS, cs_end = c.slot0 + c.nslots;
+    if (cs0 >= cs_end) return;
+    // per lane: its word (sym, eob, the next word of sym, the last bit of the previous word of eob) and what the word's step needs of its slot's record
+    LV<uint32_t> ok, s_lo, s_hi, e_lo, e_hi, n_lo, n_hi, prev, word, unit_base, nunits, scan4, table, first, word_base, work;
+    LFOR(l) {
+        const uint32_t cs = cs0 + (uint32_t(l) >> 2);
+        ok[l] = 0u; s_lo[l] = s_hi[l] = e_lo[l] = e_hi[l] = n_lo[l] = n_hi[l] = prev[l] = 0u;
+        word[l] = unit_base[l] = nunits[l] = scan4[l] = table[l] = first[l] = word_base[l] = work[l] = 0u;
+        if (cs < cs_end) {
+            const SlotRec &r = c.slots[cs];
+            const uint32_t w = 4u * r.j + (uint32_t(l) & 3u), nwords = (r.nunits_work + 63u) >> 6;
+            if ((r.flags & 1u) && w < nwords && !(c.work_active && !c.work_active[r.work])) {
+                const uint64_t *sym = c.sym_bits + r.word_base, *eob = c.eob_bits + r.word_base;
+                const uint64_t s0 = sym[w], e0 = eob[w];
+                const uint64_t s1 = w + 1 < nwords ? sym[w + 1] : ~0ull;   // behind the scan's last block: a block "with a symbol" ends the run there
+                ok[l] = 1u; s_lo[l] = uint32_t(s0); s_hi[l] = uint32_t(s0 >> 32); e_lo[l] = uint32_t(e0); e_hi[l] = uint32_t(e0 >> 32); n_lo[l] = uint32_t(s1); n_hi[l] = uint32_t(s1 >> 32);
+                prev[l] = w ? uint32_t(eob[w - 1] >> 63) : 0u;             // the scan's first block has no predecessor
+                word[l] = w; unit_base[l] = r.unit_base; nunits[l] = r.nunits_work; table[l] = r.table_base; first[l] = r.first_chunk; word_base[l] = r.word_base; work[l] = r.work;
+                scan4[l] = uint32_t(r.Ss) | (uint32_t(r.Se) << 8) | (uint32_t(r.Ah) << 16) | (uint32_t(r.Al) << 24);
+            }
+        }
+    }
+    const uint64_t okm = lballot([&](int l) { return ok[l] != 0u; });
+    if (!okm) return;
+    if ((okm & 1u) && lget(word, 0u) != 0u) CSH_ACR_PATH(6);
+    LV<uint32_t> mine, facc;   // lane nb: EOBn symbols of ordinary runs, of the slot / of the work item `acc_work`, counted so far
+    LFOR(l) { mine[l] = 0u; facc[l] = 0u; }
+    uint32_t acc_work = 0xFFFFFFFFu, acc_table = 0u;
+    auto flush_freq = [&]() { LFOR(l) if (facc[l] && l < 15) { atomicAdd(&c.tables[acc_table].freq[l << 4], facc[l]); facc[l] = 0u; } };
+    for (uint32_t q = 0; q < CSH_ACR_SLOTS; q++) {
+        if (!((okm >> (4u * q)) & 15u)) continue;
+        for (uint32_t i = 4u * q; i < 4u * q + 4u; i++) {
+            if (!((okm >> i) & 1u)) continue;
+            const uint64_t s0 = (uint64_t(lget(s_hi, i)) << 32) | lget(s_lo, i), e0 = (uint64_t(lget(e_hi, i)) << 32) | lget(e_lo, i);
+            const uint32_t wk = lget(work, i), table_base = lget(table, i);
+            if (wk != acc_work) { if (acc_work != 0xFFFFFFFFu) CSH_ACR_PATH(5); flush_freq(); acc_work = wk; acc_table = table_base; }   // (before the word's general path adds to the new table: the order does not matter, the change must not be missed)
+            if (!e0) continue;   // no block of the word ends with an EOB: none starts a run
+            const uint64_t s1 = (uint64_t(lget(n_hi, i)) << 32) | lget(n_lo, i);
+            const uint32_t prev_top = lget(prev, i), w0 = lget(word, i), ubase = lget(unit_base, i), nun = lget(nunits, i), sc4 = lget(scan4, i), first_chunk = lget(first, i), wbase = lget(word_base, i);
+            const uint32_t Ah = (sc4 >> 16) & 255u;
+            uint32_t *freq = c.tables[table_base].freq;
+            LV<int> my_nb;
+            LFOR(b) {
+                my_nb[b] = -1;
+                const uint32_t u = (w0 << 6) + uint32_t(b);
+                if (u < nun) {
+                    const int bit = b;
+                    const bool prev_eob = bit ? ((e0 >> (bit - 1)) & 1) != 0 : prev_top != 0u;
+                    const bool start = ((e0 >> bit) & 1) && (((s0 >> bit) & 1) || !prev_eob);
+                    if (start) {
+                        // next block with a symbol, looking at this word and the next one
+                        const uint64_t a0 = bit == 63 ? 0ull : (s0 & (~0ull << (bit + 1)));
+                        uint32_t next = 0xFFFFFFFFu;
+                        if (a0) next = (w0 << 6) + uint32_t(__ffsll((unsigned long long)a0) - 1);
+                        else if (s1) next = ((w0 + 1) << 6) + uint32_t(__ffsll((unsigned long long)s1) - 1);
+                        if (next != 0xFFFFFFFFu && next > nun) next = nun;
+                        const uint32_t len = next == 0xFFFFFFFFu ? 0xFFFFFFFFu : next - u;
+                        if (len <= 14u || (len < 0x7FFFu && Ah == 0)) {
+                            c.eobrun[ubase + u] = uint16_t(len);
+                            my_nb[b] = bitlen32(len) - 1;
+                            CSH_ACR_PATH(0);
+                        } else {
+                            ScanWork w; w.unit_base = ubase; w.word_base = wbase; w.nunits = nun; w.first_chunk = first_chunk; w.table_base = table_base;
+                            EncScan sc; sc.Ss = uint8_t(sc4); sc.Se = uint8_t(sc4 >> 8); sc.Ah = uint8_t(sc4 >> 16); sc.Al = uint8_t(sc4 >> 24);
+                            uint32_t t;
+                            if (eob_run_end(c.sym_bits + wbase, nun, u, CSH_LONG_RUN_WORDS, t)) {
+                                CSH_ACR_PATH(1); if (Ah) CSH_ACR_PATH(2);
+                                eob_run_serial(c, w, sc, u, t, [&](uint32_t run, uint32_t owner) {   // a run cut into sub-runs, or a long one: counted one by one
+                                    const int nb = bitlen32(run) - 1;
+                                    atomicAdd(&freq[nb << 4], 1u); atomicAdd(&c.slot_eobh[size_t(first_chunk + (owner >> 8)) * 16u + uint32_t(nb)], 1u);   // the symbol belongs to the chunk of the block that emits it
+                                });
+                            } else { CSH_ACR_PATH(4); uint32_t e = atomicAdd(c.long_cnt, 1u); c.long_runs[2 * e] = wk; c.long_runs[2 * e + 1] = u; }
+                        }
+                    }
+                }
+            }
+            // the EOBn symbol of an ordinary run (one per lane at most) is counted wave-wide: a ballot per class
+            for (int nb = 0; nb < 4; nb++) {   // runs of up to 14 blocks: EOB0 .. EOB3; longer first-pass runs below
+                const uint32_t n = popc64(lballot([&](int b) { return my_nb[b] == nb; }));
+                LFOR(l) if (l == nb) mine[l] += n;
+            }
+            if (lballot([&](int b) { return my_nb[b] >= 4; })) {
+                for (int nb = 4; nb < 15; nb++) {
+                    const uint32_t n = popc64(lballot([&](int b) { return my_nb[b] == nb; }));
+                    LFOR(l) if (l == nb) mine[l] += n;
+                }
+            }
+        }
+        // the slot's fourth word is done: its counts (atomic: the serial path of another wave may credit the same row)
+        LFOR(l) if (mine[l] && l < 15) { atomicAdd(&c.slot_eobh[size_t(cs0 + q) * 16u + uint32_t(l)], mine[l]); facc[l] += mine[l]; mine[l] = 0u; }
+    }
+    flush_freq();
 }
 // long runs (flat regions, low-quality sources: a run can span a whole scan of 32 k blocks, and a single lane walking it held
 // the kernel for a millisecond): the 64 lanes look for the end 4096 blocks at a time and cut the run 64 blocks at a time
@@ -1183,7 +1297,8 @@ void launch_zero_edges(hipStream_t st, const EncCtx &c) { if (c.nslots) CSH_LAUN
 void launch_tokens(hipStream_t st, const EncCtx &c) { if (c.nechunks) CSH_LAUNCH_PHASED(k_tokens, 6, dim3(c.nechunks), dim3(256), st, c); }
 void launch_ac_runs(hipStream_t st, const EncCtx &c) {
     if (!c.nslots) return;
-    CSH_LAUNCH(k_ac_runs, dim3((c.nslots + 3) / 4), dim3(256), st, c);
+    if (c.ac_runs_slot) CSH_LAUNCH(k_ac_runs, dim3((c.nslots + 3) / 4), dim3(256), st, c);
+    else CSH_LAUNCH(k_ac_runs_words, dim3((c.nslots + 4u * CSH_ACR_SLOTS - 1u) / (4u * CSH_ACR_SLOTS)), dim3(4 * CSP_WAVE_THREADS), st, c);
 #ifdef CSH_EMUL
     CSH_LAUNCH(k_ac_runs_long, dim3(64), dim3(1), st, c);
 #else

@@ -180,6 +180,7 @@ struct EncCtx {  // device pointers + sizes every entropy kernel needs
     const uint32_t *ref_runs;
     uint32_t nref_runs;
     uint32_t list_run;         // CSH_LIST_RUN, 1..32
+    uint32_t ac_runs_slot;     // CSH_AC_RUNS=slot: launch_ac_runs takes k_ac_runs (one wave per slot), not k_ac_runs_words (one per 16 slots)
     uint32_t nz_build, nz_filter; // the run's NzChunks: some asks for level 0 from the tiles (k_nzlist) / for a filtered level (k_nzfilter); a kernel nobody asks for is not launched
 };
 enum : uint32_t { TK_SYM = 0u, TK_RAW = 1u, TK_ACF = 2u, TK_REF = 3u, TK_EOB = 4u };   // token kinds (bits 0-2 of a token; the fields: k_entropy.hip)

@@ -29,6 +29,8 @@ thread_local int csh_emul_phase = 0;
 extern "C" void csh_emul_set_reverse(int r) { csh_emul_reverse = r; }
 namespace csh { extern int csh_emul_jacobi; }
 extern "C" void csh_emul_set_jacobi(int j) { csh::csh_emul_jacobi = j; }
+namespace csh { extern uint32_t csh_emul_ac_paths[8]; }
+extern "C" void csh_emul_ac_paths(uint32_t *out) { for (int i = 0; i < 8; i++) { out[i] = csh::csh_emul_ac_paths[i]; csh::csh_emul_ac_paths[i] = 0u; } }   // (k_entropy.hip: read and reset)
 #endif
 
 using namespace csh;
