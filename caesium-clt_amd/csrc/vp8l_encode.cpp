@@ -24,12 +24,14 @@ extern "C" int csl_encode_pixels(const csp_pixels *px, size_t count, int device,
     }
     // the coder, read on every call: unset / empty / "plain" = literals only (the bytes oracle/png_oracle.c cso_vp8l_encode states), "refs" = backward
     // references and a colour cache (k_vp8l_refs.hip), "palette" = refs, and for a picture of at most 256 colours the colour-indexing transform where that is
-    // smaller (k_vp8l_palette.hip)
+    // smaller (k_vp8l_palette.hip), "groups" = palette, and for every picture of more than one tile its refs stream with a set of codes per group of tiles where that
+    // is smaller (k_vp8l_groups.hip)
     const char *mode = getenv("CSH_VP8L");
-    const bool palette = mode && !strcmp(mode, "palette");
+    const bool groups = mode && !strcmp(mode, "groups");
+    const bool palette = groups || (mode && !strcmp(mode, "palette"));
     const bool refs = palette || (mode && !strcmp(mode, "refs"));
     if (mode && *mode && !refs && strcmp(mode, "plain")) {
-        for (size_t i = 0; i < count; i++) results[i] = make_res(CS_ERR_UNSUPPORTED, "CSH_VP8L names no lossless WebP coder (plain, refs, palette)");
+        for (size_t i = 0; i < count; i++) results[i] = make_res(CS_ERR_UNSUPPORTED, "CSH_VP8L names no lossless WebP coder (plain, refs, palette, groups)");
         return int(count);
     }
     int failed = 0;
@@ -68,7 +70,10 @@ extern "C" int csl_encode_pixels(const csp_pixels *px, size_t count, int device,
     DevBuf<uint8_t> d_modes, d_out, d_hit, d_lens;
     DevBuf<uint64_t> d_tok, d_cst;
     DevBuf<uint32_t> d_rhist, d_pick, d_pcount, d_pal;
-    DevBuf<unsigned long long> d_ptab;
+    DevBuf<unsigned long long> d_ptab, d_ginfo;
+    DevBuf<csw::Vp8lGroupImg> d_gimg;
+    DevBuf<uint32_t> d_feat, d_ghist;
+    DevBuf<uint8_t> d_label, d_glens;
     std::vector<uint32_t> len(imgs.size()), status(imgs.size());
     bool ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
     have_st = ok;
@@ -106,9 +111,29 @@ extern "C" int csl_encode_pixels(const csp_pixels *px, size_t count, int device,
     if (ok && refs)
         ok = !d_tok.alloc(work + 64) && !d_hit.alloc(work + 64) && !d_cst.alloc(cst + 64) && !d_rhist.alloc(imgs.size() * csw::VP8L_NOPT * csw::VP8L_HIST + 8) && !d_rhist.zero(st) &&
              !d_lens.alloc(imgs.size() * csw::VP8L_LENS + 8) && !d_pick.alloc(imgs.size() * 4 + 4);
+    // groups: the pictures' tiles (a picture of one tile has no grouped candidate) and the pools behind them, in this mode only
+    uint32_t max_tiles = 0;
+    if (ok && groups) {
+        std::vector<csw::Vp8lGroupImg> gimgs(nparent);
+        uint64_t tiles = 0;
+        for (size_t k = 0; k < nparent; k++) {
+            csw::Vp8lGroupImg &g = gimgs[k];
+            const uint32_t b = csw::vp8l_group_bits(imgs[k].width, imgs[k].height);
+            g.tw = (imgs[k].width + (1u << b) - 1) >> b; g.th = (imgs[k].height + (1u << b) - 1) >> b; g.ntile = g.tw * g.th;
+            g.bits = g.ntile > 1 ? b : 0u;
+            g.tile_off = tiles; tiles += (g.ntile + 63) & ~uint64_t(63);
+            if (g.bits) max_tiles = std::max(max_tiles, g.ntile);
+        }
+        ok = !d_gimg.upload(gimgs, st) && !d_label.alloc(tiles + 64) && !d_feat.alloc(tiles * csw::VP8L_TILE_FEAT + 64) &&
+             !d_ghist.alloc(nparent * csw::VP8L_MAX_GROUPS * csw::VP8L_HIST + 8) && !d_ghist.zero(st) && !d_glens.alloc(nparent * csw::VP8L_MAX_GROUPS * csw::VP8L_LENS + 8) &&
+             !d_ginfo.alloc(nparent * csw::VP8L_GROUP_INFO + 8) && !d_ginfo.zero(st);
+    }
     if (ok) {
-        const csw::Vp8lRefs pools = {d_tok.p, d_hit.p, d_cst.p, d_rhist.p, d_lens.p, d_pick.p};
-        if (palette)
+        const csw::Vp8lRefs pools = {d_tok.p, d_hit.p, d_cst.p, d_rhist.p, d_lens.p, d_pick.p, d_gimg.p, d_label.p, d_feat.p, d_ghist.p, d_glens.p, d_ginfo.p};
+        if (groups)
+            csw::launch_vp8l_encode_groups(st, d_imgs.p, int(nparent), int(imgs.size() - nparent), max_blocks, max_px, max_packed, max_tiles, d_ptab.p, d_pal.p, d_work.p, d_modes.p, d_hist.p,
+                                           pools, d_out.p, d_len.p, d_status.p);
+        else if (palette)
             csw::launch_vp8l_encode_palette(st, d_imgs.p, int(nparent), int(imgs.size() - nparent), max_blocks, max_px, max_packed, d_ptab.p, d_pal.p, d_work.p, d_modes.p, d_hist.p, pools, d_out.p,
                                             d_len.p, d_status.p);
         else if (refs)

@@ -76,7 +76,14 @@ struct Vp8lRefs {
     uint64_t *cst;         // cache contents (cst_off)
     uint32_t *hist;        // per picture VP8L_NOPT x VP8L_HIST counts, zeroed by the caller
     uint8_t *lens;         // per picture VP8L_LENS
-    uint32_t *pick;        // per record 4 words: who writes (0 the plain pack, 1 the refs pack, 2 neither: another record of the picture does), the option, the two streams' bits behind the head
+    uint32_t *pick;        // per record 4 words: who writes (0 the plain pack, 1 the refs pack, 2 neither: another record of the picture does, 3 the groups pack), the option, the two streams' bits behind the head
+    // CSH_VP8L=groups only (k_vp8l_groups.hip); nullptr in the other modes
+    const struct Vp8lGroupImg *gimg;   // per picture: its tiles
+    uint8_t *label;        // per tile its group (Vp8lGroupImg::tile_off)
+    uint32_t *feat;        // per tile VP8L_TILE_FEAT folded counts
+    uint32_t *ghist;       // per picture VP8L_MAX_GROUPS x VP8L_HIST counts of the chosen option, zeroed by the caller
+    uint8_t *glens;        // per picture VP8L_MAX_GROUPS x VP8L_LENS
+    unsigned long long *ginfo;   // per picture VP8L_GROUP_INFO words: the number of groups (0: no grouped candidate), then every group's bits (descriptions and symbols)
 };
 void launch_vp8l_encode_refs(hipStream_t st, const Vp8lImg *imgs, int nimg, uint32_t max_blocks, uint64_t max_pixels, uint32_t *work, uint8_t *modes, uint32_t *hist, const Vp8lRefs &refs,
                              uint8_t *out, uint32_t *file_len, uint32_t *status);
@@ -104,6 +111,30 @@ void launch_vp8l_encode_palette(hipStream_t st, const Vp8lImg *imgs, int nparent
 // itself passes candidates by)
 void launch_vp8l_pack_candidates(hipStream_t st, const Vp8lImg *imgs, int first, int nimg, const uint32_t *work, const uint8_t *modes, const uint32_t *hist, const uint32_t *pick, uint8_t *out,
                                  uint32_t *file_len, uint32_t *status);
+// the meta prefix (entropy) image (CSH_VP8L=groups, k_vp8l_groups.hip): everything CSH_VP8L=palette does, and for every picture one more candidate, its refs stream
+// coded with up to VP8L_MAX_GROUPS sets of five prefix codes, one set per tile of (1 << bits)^2 pixels; written where it is strictly the smallest
+enum : uint32_t {
+    VP8L_MAX_GROUPS = 8,
+    VP8L_MAX_TILES = 4096,                // per picture: the tile side is the smallest of 32 .. 512 that keeps to it
+    VP8L_TILE_FEAT = 64,                  // folded counts per tile: 15 magnitude classes for each of green, red, blue, alpha; cache hits; copies; two unused
+    VP8L_GROUP_INFO = 16,
+};
+struct Vp8lGroupImg {
+    uint32_t bits;         // the tile side's log2, 5 .. 9; 0: the picture is one tile and has no grouped candidate
+    uint32_t tw, th, ntile;
+    uint64_t tile_off;     // the picture's first tile in the label pool (x VP8L_TILE_FEAT: in the feature pool)
+};
+__host__ __device__ static inline uint32_t vp8l_group_bits(uint32_t width, uint32_t height) {
+    for (uint32_t b = 5; b < 9; b++) if (uint64_t((width + (1u << b) - 1) >> b) * ((height + (1u << b) - 1) >> b) <= VP8L_MAX_TILES) return b;
+    return 9u;             // 16384 x 16384: 32 x 32 tiles
+}
+// behind launch_vp8l_refs_stages, for the pictures 0 .. nimg - 1: tile features, clustering, group histograms, group codes, the choice (pick[4 i] = 3 where the grouped
+// stream is strictly smaller than the picture's two others); then the pack of those pictures
+void launch_vp8l_group_stages(hipStream_t st, const Vp8lImg *imgs, int nimg, uint32_t max_tiles, const uint32_t *work, const Vp8lRefs &refs);
+void launch_vp8l_pack_groups(hipStream_t st, const Vp8lImg *imgs, int nimg, const uint32_t *work, const uint8_t *modes, const Vp8lRefs &refs, uint8_t *out, uint32_t *file_len, uint32_t *status);
+// launch_vp8l_encode_palette with the group stages between the refs stages and the palette's choice; max_tiles: the largest Vp8lGroupImg::ntile
+void launch_vp8l_encode_groups(hipStream_t st, const Vp8lImg *imgs, int nparent, int ncand, uint32_t max_blocks, uint64_t max_pixels, uint64_t max_packed, uint32_t max_tiles,
+                               const unsigned long long *tabs, uint32_t *pal, uint32_t *work, uint8_t *modes, uint32_t *hist, const Vp8lRefs &refs, uint8_t *out, uint32_t *file_len, uint32_t *status);
 // pieces of launch_vp8l_encode (k_vp8l_enc.hip) the refs coder runs as they are: the front end, and the plain pack for the pictures whose pick[4 i] is 0 (pick = nullptr: all)
 void launch_vp8l_front(hipStream_t st, const Vp8lImg *imgs, int nimg, uint32_t max_blocks, uint64_t max_pixels, uint32_t *work, uint8_t *modes, uint32_t *hist);
 void launch_vp8l_pack_plain(hipStream_t st, const Vp8lImg *imgs, int nimg, const uint32_t *work, const uint8_t *modes, const uint32_t *hist, const uint32_t *pick, uint8_t *out, uint32_t *file_len,

@@ -1,5 +1,6 @@
 """Time csl_encode_pixels (pixels in device memory -> lossless WebP files) in its coders, in one process: CSH_VP8L=plain (literals only), CSH_VP8L=refs
-(backward references and a colour cache), CSH_VP8L=palette (refs, and the colour-indexing transform for pictures of at most 256 colours).  96 pictures of
+(backward references and a colour cache), CSH_VP8L=palette (refs, and the colour-indexing transform for pictures of at most 256 colours), CSH_VP8L=groups
+(palette, and an entropy image of up to eight groups of prefix codes).  96 pictures of
 1920 x 1080 by default: photographic (three textures) and graphic content, repeated.
 
     python tools/vp8l_refs_time.py [--count 96] [--width 1920] [--height 1080] [--repeats 3] [--once] [--modes plain,refs] [--dithered 0]
