@@ -787,7 +787,7 @@ int cso_forward(const uint8_t *pix, int w, int h, int ncomp, const cso_enc_param
 /* optimal Huffman table: libjpeg jpeg_gen_optimal_table behaviour (T.81 K.2 + libjpeg's      */
 /* pseudo-symbol 256 and 16-bit length limiting)                               */
 int cso_gen_optimal_table(const long freq_in[257], uint8_t bits_out[17], uint8_t huffval[256]) {
-    long freq[257]; int codesize[257], others[257]; uint8_t bits[33];
+    long freq[257]; int codesize[257], others[257]; int bits[33];   /* (int: 255 symbols and the reserved entry can all have 8 bits, which a byte counts as 0) */
     memcpy(freq, freq_in, sizeof freq);
     memset(bits, 0, sizeof bits); memset(codesize, 0, sizeof codesize);
     for (int i = 0; i < 257; i++) others[i] = -1;
@@ -809,9 +809,10 @@ int cso_gen_optimal_table(const long freq_in[257], uint8_t bits_out[17], uint8_t
             int j = i - 2; while (bits[j] == 0) j--;
             bits[i] -= 2; bits[i - 1]++; bits[j + 1] += 2; bits[j]--;
         }
-    int i = 16; while (bits[i] == 0) i--;
-    bits[i]--;
-    memcpy(bits_out, bits, 17); bits_out[0] = 0;
+    int i = 16; while (i > 0 && bits[i] == 0) i--;   /* an all-zero table has no length at all: nothing to remove */
+    if (i > 0) bits[i]--;
+    for (int l = 1; l <= 16; l++) bits_out[l] = (uint8_t)bits[l];   /* at most 255 once the reserved code point is gone */
+    bits_out[0] = 0;
     int p = 0;
     for (int l = 1; l <= 32; l++) for (int s = 0; s <= 255; s++) if (codesize[s] == l) huffval[p++] = (uint8_t)s;
     return p;

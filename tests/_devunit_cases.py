@@ -2,8 +2,9 @@
 checking function per unit.  tests/test_device_units_emul.py drives the emulation build of the library through it, tests/test_device_units_gpu.py the
 gfx950 build -- the same bytes in, the same values expected, so the two branches of a CSH_EMUL conditional answer to one statement.
 
-Where the expected values come from: numpy / Python integer arithmetic written here from the operation's definition, and the oracle's plain routines
-cso_fdct_islow, cso_idct_islow and cso_dering_block.  Never from either build of the library, nor from another function of the file under test.
+Where the expected values come from: numpy / Python integer arithmetic written here from the operation's definition, the oracle's plain routines
+cso_fdct_islow, cso_idct_islow and cso_dering_block, and for the prefix codes tests/_prefix_model.py (T.81 K.2 in Python integers).  Never from either build of
+the library, nor from another function of the file under test.
 Every comparison is exact."""
 import ctypes as C
 import functools
@@ -740,6 +741,175 @@ def unit_dither_dist(lib):
     assert (per[:, -1:] > per[:, :-1]).all(), "k_png_dither's padding entry is not farther than every real palette entry"
 
 
+# ---------------------------------------------------------------------------------------------------- prefix codes from histograms
+# The three builders (k_gen_tables; csp::code_lengths + canonical; csw::code_lengths_wide) against tests/_prefix_model.py, the Python statement of T.81 K.2,
+# on histograms shaped to bend them: the limit binding, one or two symbols, nothing at all, ties everywhere, every symbol used, depths near 32.
+CODE_ALPHABETS = [(286, 15), (30, 15), (19, 7), (280, 15), (256, 15), (40, 15), (8, 15)]   # DEFLATE lit/len, dist, code lengths; VP8L green, red / blue / alpha, distance, the group labels
+WIDE_ALPHABETS = [280, 536, 1304]   # the green alphabet without a colour cache, with one of 256 entries, with the largest (VP8L_GREEN_MAX)
+JPEG_MAX_DEPTH, JPEG_MAX_TOTAL = 32, 10 ** 9   # what libjpeg's jpeg_gen_optimal_table accepts (its 32 counters, its 1000000000 sentinel): the domain k_gen_tables is tested on
+
+
+def _fib(k):
+    f = [1, 1]
+    while len(f) < k: f.append(f[-1] + f[-2])
+    return f[:k]
+
+
+def _pow17(k):
+    return [17 ** i // 10 ** i + 1 for i in range(k)]   # int(1.7^i) + 1 in exact arithmetic: no two alike, each more than the sum of the two before the last -> depth k - 1
+
+
+@functools.lru_cache(None)
+def prefix_battery(n, wide=False):
+    """[(name, [n frequencies])] for an alphabet of n symbols, the same shapes for every n (those that need more symbols than n has are left out).
+    Symbols are placed by a seeded permutation unless the name says where they are."""
+    rng = np.random.default_rng(1000 + n)
+    cases = []
+
+    def add(name, values, at=None):
+        values = [int(v) for v in values]
+        if len(values) > n: return
+        f = [0] * n
+        for p, v in zip(rng.permutation(n)[:len(values)].tolist() if at is None else at, values): f[p] = v
+        assert sum(f) < 1 << 32
+        cases.append((name, f))
+    add("empty", [])
+    add("one symbol", [5])
+    add("one symbol, the first", [5], at=[0])
+    add("one symbol, the second", [5], at=[1])
+    add("one symbol, the last", [5], at=[n - 1])
+    add("two equal symbols", [9, 9])
+    add("three 1s", [1, 1, 1])
+    add("the first and the last symbol only", [3, 4], at=[0, n - 1])
+    add("every symbol once", [1] * n)
+    add("all but one symbol, 7 times each", [7] * (n - 1))
+    for k in range(2, 31): add(f"2^i over {k}", [1 << i for i in range(k)])
+    for k in range(2, 34): add(f"1.7^i over {k}", _pow17(k))   # (33: with JPEG's reserved entry, a depth of exactly 32)
+    for k in (5, 10, 16, 17, 19, 25, 40): add(f"Fibonacci {k}", _fib(k))
+    add("200 of 1000 and a 1.7^i tail of 30", [1000] * 200 + _pow17(30))
+    for d in range(60):
+        u, top, k = float(rng.uniform(0.5, 5)), 10 ** float(rng.uniform(2, 6)), int(rng.integers(2, n + 1))
+        add(f"geometric {d}: rate 10^-{u:.2f} over {k}", [v for v in (int(top * np.exp(-(10 ** -u) * i)) for i in range(k)) if v] or [1])
+    for d in range(20):
+        add(f"1, 2, 3 draw {d}", rng.integers(1, 4, int(rng.integers(2, n + 1))).tolist())
+    if wide:
+        add("every symbol, 1, 2 or 3 times", rng.integers(1, 4, n).tolist())
+        add(f"{n - 30} of 1000 and a 1.7^i tail of 30", [1000] * (n - 30) + _pow17(30))
+        add(f"{n - 40} of 1000 and Fibonacci 40", [1000] * (n - 40) + _fib(40))
+    return cases
+
+
+def battery_coverage(cases, n, limit, depths):
+    """the battery's own conditions: the histograms that empty, fill and bend a code are all there.  A condition, not a measurement."""
+    used = [sum(1 for v in f if v) for _, f in cases]
+    for want in (0, 1, 2, n):
+        assert want in used, f"alphabet {n}: no case with {want} symbols used"
+    binding = sum(1 for d in depths if d > limit)
+    if n > limit + 1:
+        assert binding >= 20, f"alphabet {n}, limit {limit}: the limit binds in {binding} cases only"
+    else:
+        assert binding == 0   # n symbols make a depth of at most n - 1: this alphabet cannot reach its limit
+    return binding
+
+
+@functools.lru_cache(None)
+def jpeg_battery():
+    """the 256-symbol battery within libjpeg's domain (depth, the reserved entry included, at most 32; total below 10^9) -> [(name, freq)], [model tables]"""
+    import _prefix_model as M
+    keep, tabs = [], []
+    for name, f in prefix_battery(256):
+        t = M.jpeg_table(f)
+        if t[4] <= JPEG_MAX_DEPTH and sum(f) < JPEG_MAX_TOTAL:
+            keep.append((name, f)); tabs.append(t)
+    battery_coverage(keep, 256, 16, [t[4] for t in tabs])
+    assert max(t[4] for t in tabs) == JPEG_MAX_DEPTH
+    return keep, tabs
+
+
+def enctable_dtype(lib):
+    """DevEncTable (types.h) with its offsets written out: natural alignment of uint32 / uint16 / int members, checked against the library's sizeof"""
+    dt = np.dtype({"names": ["freq", "bits", "vals", "code", "size", "nsym", "lut"],
+                   "formats": [("<u4", 257), ("u1", 17), ("u1", 256), ("<u2", 256), ("u1", 256), "<i4", ("<u4", 256)],
+                   "offsets": [0, 1028, 1045, 1302, 1814, 2072, 2076], "itemsize": 3100})
+    lib.dll.csdu_sizeof_enctable.restype = C.c_size_t
+    assert lib.dll.csdu_sizeof_enctable() == dt.itemsize, (lib.dll.csdu_sizeof_enctable(), dt.itemsize)
+    return dt
+
+
+def unit_gen_tables(lib, count):
+    """k_gen_tables: `count` tables in one launch (0: the whole battery) -- bits, nsym, vals, code, size and lut exactly the model's.  freq[256] holds junk on the
+    way in (the kernel must set the reserved entry itself), and everything behind freq is filled with 0xA5 (the kernel must write all of it)."""
+    cases, tabs = jpeg_battery()
+    if count:
+        names = [name for name, _ in cases]
+        pick = [names.index(w) for w in ("1.7^i over 24", "empty", "every symbol once", "one symbol", "Fibonacci 25")[:count]]   # (the first one binds the limit)
+        cases, tabs = [cases[i] for i in pick], [tabs[i] for i in pick]
+    dt = enctable_dtype(lib)
+    T = np.frombuffer(np.full(len(cases) * dt.itemsize, 0xA5, np.uint8).tobytes(), dt).copy()
+    for i, (_, f) in enumerate(cases):
+        T["freq"][i, :256] = f
+        T["freq"][i, 256] = 0xDEADBEEF if i % 2 else 0
+    lib.run("csdu_gen_tables", len(cases), T.view(np.uint8))
+    name = f"k_gen_tables [{len(cases)} tables in one launch]"
+    W = np.zeros(len(cases), dt)
+    for i, (bits, vals, code, size, _) in enumerate(tabs):
+        W["bits"][i], W["code"][i], W["size"][i], W["nsym"][i] = bits, code, size, len(vals)
+        W["vals"][i, :len(vals)] = vals
+        W["lut"][i] = (np.array(size, np.uint32) << 16) | np.array(code, np.uint32)
+    same(f"{name}: nsym", T["nsym"], W["nsym"])
+    same(f"{name}: bits", T["bits"], W["bits"])
+    listed = np.arange(256)[None, :] < W["nsym"][:, None]
+    same(f"{name}: vals[:nsym]", np.where(listed, T["vals"], 0), W["vals"])
+    for k in ("code", "size", "lut"): same(f"{name}: {k}", T[k], W[k])
+    same(f"{name}: the counts of the 256 symbols are left as they were", T["freq"][:, :256], np.array([f for _, f in cases], np.uint32))
+
+
+def _code_inputs(n, wide=False):
+    cases = prefix_battery(n, wide)
+    return cases, np.ascontiguousarray(np.array([f for _, f in cases], np.uint32))
+
+
+def unit_code_lengths(lib, n, limit):
+    """csp::code_lengths + csp::canonical, a lane per case: the model's lengths, RFC 1951's codes bit-reversed"""
+    import _prefix_model as M
+    cases, F = _code_inputs(n)
+    L, K = np.zeros(F.shape, np.uint8), np.zeros(F.shape, np.uint16)
+    lib.run("csdu_code_lengths", len(cases), n, limit, F, L, K)
+    want = [M.limited_lengths(f, limit) for _, f in cases]
+    battery_coverage(cases, n, limit, [d for _, d in want])
+    name = f"csp::code_lengths [{n} symbols, at most {limit} bits, {len(cases)} cases]"
+    same(f"{name}: the lengths", L, np.array([l for l, _ in want], np.uint8))
+    same(f"{name}: canonical(), the codes", K, np.array([M.deflate_codes(l) for l, _ in want], np.uint16))
+
+
+def unit_code_lengths_wide(lib, n):
+    """csw::code_lengths_wide, a wave per case with lane 0 at work in LDS: the model's lengths, and csp::code_lengths' own where that one holds the alphabet"""
+    import _prefix_model as M
+    cases, F = _code_inputs(n, True)
+    L = np.zeros(F.shape, np.uint8)
+    lib.run("csdu_code_lengths_wide", len(cases), n, 15, F, L)
+    want = [M.limited_lengths(f, 15) for _, f in cases]
+    battery_coverage(cases, n, 15, [d for _, d in want])
+    assert any(all(f) and d > 15 for (_, f), (_, d) in zip(cases, want)), "no case with every symbol used AND the limit binding"
+    name = f"csw::code_lengths_wide [{n} symbols, {len(cases)} cases]"
+    same(f"{name}: the lengths", L, np.array([l for l, _ in want], np.uint8))
+    if n <= 288:
+        L2, K2 = np.zeros(F.shape, np.uint8), np.zeros(F.shape, np.uint16)
+        lib.run("csdu_code_lengths", len(cases), n, 15, F, L2, K2)
+        same(f"{name}: the same lengths as csp::code_lengths", L, L2)
+
+
+def unit_code_entries_refuse(lib):
+    """a call the functions' fixed arrays do not hold is refused before anything is launched"""
+    f, l, k = np.ones(4 * 2000, np.uint32), np.zeros(4 * 2000, np.uint8), np.zeros(4 * 2000, np.uint16)
+    for n, limit in ((289, 15), (1, 15), (19, 6), (19, 16), (286, 8), (0, 15), (-5, 15)):
+        assert lib.call("csdu_code_lengths", 1, n, limit, f, l, k) == -1, (n, limit)
+    for n, limit in ((1305, 15), (1, 15), (280, 6), (280, 16), (280, 8), (1304, 10)):
+        assert lib.call("csdu_code_lengths_wide", 1, n, limit, f, l) == -1, (n, limit)
+    assert lib.call("csdu_code_lengths", 0, 19, 7, f, l, k) == -1 and lib.call("csdu_code_lengths_wide", 0, 280, 15, f, l) == -1
+    assert lib.call("csdu_gen_tables", 0, f) == -1
+
+
 # ---------------------------------------------------------------------------------------------------- the list
 def _units():
     u = {}
@@ -763,6 +933,10 @@ def _units():
         u[f"wave_or64-{nt}"] = functools.partial(unit_or64, nthreads=nt)
     for nt in (64, 65, 96, 256):
         for op in (3, 4): u[f"{['wave_last', 'wave_last_of_scan'][op - 3]}-{nt}"] = functools.partial(unit_escan, op=op, nthreads=nt)
+    for count in (1, 4, 5, 0): u[f"gen_tables-{count or 'all'}"] = functools.partial(unit_gen_tables, count=count)
+    for n, limit in CODE_ALPHABETS: u[f"code_lengths-{n}-{limit}"] = functools.partial(unit_code_lengths, n=n, limit=limit)
+    for n in WIDE_ALPHABETS: u[f"code_lengths_wide-{n}"] = functools.partial(unit_code_lengths_wide, n=n)
+    u["code_entries_refuse"] = unit_code_entries_refuse
     u["load_unaligned_align_bytes"] = unit_lz
     u["dither_distance"] = unit_dither_dist
     return u

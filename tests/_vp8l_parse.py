@@ -4,6 +4,10 @@ literals / cache hits / backward references code the picture, every (length, dis
 
     info = parse(blob)          # blob: a RIFF file with a VP8L chunk, or a bare VP8L payload with headerless=(width, height)
     info.cache_bits, info.literals, info.cache_hits, info.refs -> [(length, distance, position)], info.argb -> (h, w) uint32 array
+    info.codes -> [(where, group, which, Code)] of every prefix code in the stream, in stream order: where "argb" (the picture), "meta" (the entropy image) or
+                  "transform"; which 0 .. 4 (green, red, blue, alpha, distance).  A Code keeps its lengths and how often each symbol was read with it (count); a
+                  normally coded one (not simple) also the code-length code that described it (cl_lengths), the use of ITS symbols (cl_count) and
+                  whether the description states how many lengths it lists (cl_counted)
 """
 import numpy as np
 
@@ -39,6 +43,7 @@ class Code:
     """canonical prefix code from code lengths; the stream carries a code's bits from its most significant one"""
 
     def __init__(self, lengths):
+        self.lengths, self.count, self.simple, self.cl_lengths, self.cl_count = list(lengths), [0] * len(lengths), False, None, None
         used = [(l, s) for s, l in enumerate(lengths) if l]
         assert used, "a code without symbols"
         self.single = used[0][1] if len(used) == 1 else None
@@ -60,9 +65,11 @@ class Code:
 
     def read(self, br):
         if self.single is not None:
+            self.count[self.single] += 1
             return self.single
         s, l = self.table[br.peek(self.maxlen)]
         br.pos += l
+        self.count[s] += 1
         return s
 
 
@@ -74,14 +81,17 @@ def read_code(br, alphabet):
         lengths[s0] = 1
         if n == 2:
             lengths[br.read(8)] = 1
-        return Code(lengths)
+        c = Code(lengths)
+        c.simple = True
+        return c
     ncl = 4 + br.read(4)
     cl = [0] * 19
     for i in range(ncl):
         cl[CODE_LENGTH_ORDER[i]] = br.read(3)
     cc = Code(cl)
-    max_symbol = alphabet
+    max_symbol, counted = alphabet, False
     if br.read(1):
+        counted = True
         max_symbol = 2 + br.read(2 + 2 * br.read(3))
         assert max_symbol <= alphabet
     s, prev = 0, 8
@@ -99,7 +109,9 @@ def read_code(br, alphabet):
             if v == 16:
                 lengths[s:s + rep] = [prev] * rep
             s += rep
-    return Code(lengths)
+    c = Code(lengths)
+    c.cl_lengths, c.cl_count, c.cl_counted = cl, cc.count, counted   # cl_counted: the stream says how many lengths follow
+    return c
 
 
 def prefix_value(br, sym):
@@ -113,18 +125,20 @@ class Stats:
     pass
 
 
-def read_pixels(br, w, h, level0, st=None):
-    """an entropy-coded ARGB image -> list of w * h values; st (level 0 only) receives the counts"""
+def read_pixels(br, w, h, level0, st=None, codes=None, where="transform"):
+    """an entropy-coded ARGB image -> list of w * h values; st (level 0 only) receives the counts; codes: a list that receives (where, group, which, Code)"""
     cache_bits = br.read(4) if br.read(1) else 0
     assert cache_bits == 0 or 1 <= cache_bits <= 11
     prec, meta, mw, ngroups = 0, None, 0, 1
     if level0 and br.read(1):
         prec = br.read(3) + 2
         mw, mh = -(-w >> prec), -(-h >> prec)
-        meta = [(v >> 8) & 0xFFFF for v in read_pixels(br, mw, mh, False)]
+        meta = [(v >> 8) & 0xFFFF for v in read_pixels(br, mw, mh, False, codes=codes, where="meta")]
         ngroups = max(meta) + 1
     csize = (1 << cache_bits) if cache_bits else 0
     groups = [[read_code(br, n) for n in (256 + 24 + csize, 256, 256, 256, 40)] for _ in range(ngroups)]
+    if codes is not None:
+        codes += [("argb" if level0 else where, gi, k, c) for gi, g in enumerate(groups) for k, c in enumerate(g)]
     cache = [0] * csize
     out = [0] * (w * h)
     n, pos, shift = w * h, 0, 32 - cache_bits
@@ -244,7 +258,7 @@ def parse(blob, headerless=None):
     else:
         br = Bits(blob)
         W, H = headerless
-    transforms, xs, seen = [], W, set()
+    transforms, xs, seen, codes = [], W, set(), []
     while br.read(1):
         t = br.read(2)
         assert t not in seen
@@ -252,19 +266,20 @@ def parse(blob, headerless=None):
         if t in (0, 1):
             bits = br.read(3) + 2
             bw, bh = -(-xs >> bits), -(-H >> bits)
-            transforms.append((t, bits, xs, read_pixels(br, bw, bh, False)))
+            transforms.append((t, bits, xs, read_pixels(br, bw, bh, False, codes=codes)))
         elif t == 2:
             transforms.append((t, 0, xs, None))
         else:
             ncol = br.read(8) + 1
-            pal = read_pixels(br, ncol, 1, False)
+            pal = read_pixels(br, ncol, 1, False, codes=codes)
             for i in range(1, ncol):
                 pal[i] = _add(pal[i], pal[i - 1])
             bits = 0 if ncol > 16 else 1 if ncol > 4 else 2 if ncol > 2 else 3
             transforms.append((t, bits, xs, pal))
             xs = -(-xs >> bits)
     st = Stats()
-    px = read_pixels(br, xs, H, True, st)
+    px = read_pixels(br, xs, H, True, st, codes=codes)
+    st.codes = codes
     st.width, st.height, st.transforms, st.payload_bits = W, H, [t[0] for t in transforms], br.pos
     for t, bits, tw, data in reversed(transforms):
         if t == 2:

@@ -1,5 +1,5 @@
 // du_entropy.cpp -- device units over caesium-clt_amd/csrc/k_entropy.hip: its DPP scans (wave_scan_dpp with + and |, wave_incl_scan), wave_or64, wave_last
-// and pk_abs16.  Here a thread is a lane in both builds.  wave_scan_dpp and wave_last exist in the product build only (the emulation, whose lanes run one
+// and pk_abs16, and the whole of k_gen_tables through its launcher.  In the scan units a thread is a lane in both builds.  wave_scan_dpp and wave_last exist in the product build only (the emulation, whose lanes run one
 // after the other, has nothing to put there): their entries answer CSDU_DEVICE_ONLY from the emulation build.  See du_common.h.
 #include "../../caesium-clt_amd/csrc/k_entropy.hip"
 #include "du_common.h"
@@ -65,5 +65,18 @@ int csdu_abs16(int n, const uint32_t *in, uint32_t *out) {
     CSH_LAUNCH(k_du_abs16, dim3(unsigned((n + 255) / 256)), dim3(256), 0, n, d_in, d_o);
     DU_TRY(du_finish());
     return du_download(out, d_o, size_t(n) * 4);
+}
+// k_gen_tables as the pipeline launches it: a wave per table, four to a workgroup (the last one partly filled unless ntables % 4 == 0).  tables: in, freq[0..255]
+// (the kernel sets freq[256] itself); out, everything behind it.  The struct is the library's own: the caller checks its layout against csdu_sizeof_enctable().
+size_t csdu_sizeof_enctable() { return sizeof(DevEncTable); }
+int csdu_gen_tables(int ntables, DevEncTable *tables) {
+    if (ntables <= 0) return -1;
+    DuBufs B;
+    DevEncTable *d_t;
+    const size_t nb = size_t(ntables) * sizeof(DevEncTable);
+    DU_TRY(B.upload(&d_t, tables, nb));
+    launch_gen_tables(0, d_t, ntables);
+    DU_TRY(du_finish());
+    return du_download(tables, d_t, nb);
 }
 }

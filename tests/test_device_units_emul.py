@@ -16,7 +16,7 @@ def test_units_do_not_depend_on_the_order_of_the_lanes():
     lib = DU.emul_lib()
     lib.dll.csdu_set_reverse(1)
     try:
-        for unit in ("dering-1-256", "fdct-2-64", "lscan-256", "LeReader-256", "wave_incl_scan-256"):
+        for unit in ("dering-1-256", "fdct-2-64", "lscan-256", "LeReader-256", "wave_incl_scan-256", "gen_tables-5", "code_lengths-19-7", "code_lengths_wide-536"):
             DU.UNITS[unit](lib)
     finally:
         lib.dll.csdu_set_reverse(0)
