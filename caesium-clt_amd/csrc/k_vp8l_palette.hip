@@ -165,9 +165,10 @@ void launch_vp8l_pal_count(hipStream_t st, const Vp8lImg *imgs, int nimg, uint64
     CSH_LAUNCH(k_vp8l_pal_count, dim3(unsigned((max_pixels + VP8L_PAL_STRIP - 1) / VP8L_PAL_STRIP), unsigned(nimg)), dim3(CSP_WAVE_THREADS), st, imgs, tabs, count);
 }
 
-// max_tiles != 0: CSH_VP8L=groups
+// max_tiles != 0: CSH_VP8L=groups; far: CSH_VP8L=far
 static void encode_palette(hipStream_t st, const Vp8lImg *imgs, int nparent, int ncand, uint32_t max_blocks, uint64_t max_pixels, uint64_t max_packed, uint32_t max_tiles,
-                           const unsigned long long *tabs, uint32_t *pal, uint32_t *work, uint8_t *modes, uint32_t *hist, const Vp8lRefs &R, uint8_t *out, uint32_t *file_len, uint32_t *status) {
+                           const unsigned long long *tabs, uint32_t *pal, uint32_t *work, uint8_t *modes, uint32_t *hist, const Vp8lRefs &R, const Vp8lFar *far, uint8_t *out, uint32_t *file_len,
+                           uint32_t *status) {
     const int nimg = nparent + ncand;
     if (!nimg) return;
     if (ncand) {
@@ -176,6 +177,7 @@ static void encode_palette(hipStream_t st, const Vp8lImg *imgs, int nparent, int
     }
     launch_vp8l_refs_stages(st, imgs, nimg, max_blocks, max_pixels, work, modes, hist, R);
     if (max_tiles) launch_vp8l_group_stages(st, imgs, nparent, max_tiles, work, R);   // in front of the palette's choice: it compares with the picture's best
+    if (far) launch_vp8l_far_stages(st, imgs, nparent, nimg, max_pixels, max_tiles, work, hist, R, *far);   // every record's better token set, in the first set's pools
     if (ncand) CSH_LAUNCH(k_vp8l_pal_choose, dim3(unsigned(ncand)), dim3(CSP_WAVE_THREADS), st, imgs, nparent, modes, R.pick);
     launch_vp8l_refs_packs(st, imgs, nimg, work, modes, hist, R, out, file_len, status);
     launch_vp8l_pack_candidates(st, imgs, nparent, nimg, work, modes, hist, R.pick, out, file_len, status);
@@ -183,11 +185,16 @@ static void encode_palette(hipStream_t st, const Vp8lImg *imgs, int nparent, int
 }
 void launch_vp8l_encode_palette(hipStream_t st, const Vp8lImg *imgs, int nparent, int ncand, uint32_t max_blocks, uint64_t max_pixels, uint64_t max_packed, const unsigned long long *tabs,
                                 uint32_t *pal, uint32_t *work, uint8_t *modes, uint32_t *hist, const Vp8lRefs &R, uint8_t *out, uint32_t *file_len, uint32_t *status) {
-    encode_palette(st, imgs, nparent, ncand, max_blocks, max_pixels, max_packed, 0u, tabs, pal, work, modes, hist, R, out, file_len, status);
+    encode_palette(st, imgs, nparent, ncand, max_blocks, max_pixels, max_packed, 0u, tabs, pal, work, modes, hist, R, nullptr, out, file_len, status);
 }
 void launch_vp8l_encode_groups(hipStream_t st, const Vp8lImg *imgs, int nparent, int ncand, uint32_t max_blocks, uint64_t max_pixels, uint64_t max_packed, uint32_t max_tiles,
                                const unsigned long long *tabs, uint32_t *pal, uint32_t *work, uint8_t *modes, uint32_t *hist, const Vp8lRefs &R, uint8_t *out, uint32_t *file_len, uint32_t *status) {
-    encode_palette(st, imgs, nparent, ncand, max_blocks, max_pixels, max_packed, max_tiles, tabs, pal, work, modes, hist, R, out, file_len, status);
+    encode_palette(st, imgs, nparent, ncand, max_blocks, max_pixels, max_packed, max_tiles, tabs, pal, work, modes, hist, R, nullptr, out, file_len, status);
+}
+void launch_vp8l_encode_far(hipStream_t st, const Vp8lImg *imgs, int nparent, int ncand, uint32_t max_blocks, uint64_t max_pixels, uint64_t max_packed, uint32_t max_tiles,
+                            const unsigned long long *tabs, uint32_t *pal, uint32_t *work, uint8_t *modes, uint32_t *hist, const Vp8lRefs &R, const Vp8lFar &far, uint8_t *out, uint32_t *file_len,
+                            uint32_t *status) {
+    encode_palette(st, imgs, nparent, ncand, max_blocks, max_pixels, max_packed, max_tiles, tabs, pal, work, modes, hist, R, &far, out, file_len, status);
 }
 
 }  // namespace csw

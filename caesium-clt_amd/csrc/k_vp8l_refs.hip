@@ -385,6 +385,12 @@ void launch_vp8l_refs_stages(hipStream_t st, const Vp8lImg *imgs, int nimg, uint
     CSH_LAUNCH_PHASED(k_vp8l_refs_hist, 3, dim3(max_chunks, unsigned(nimg)), dim3(256), st, imgs, work, R.tok, R.hit, R.hist);
     CSH_LAUNCH(k_vp8l_refs_codes, dim3(unsigned(nimg)), dim3(CSP_WAVE_THREADS), st, imgs, nimg, hist, R.hist, R.lens, R.pick);
 }
+void launch_vp8l_token_stages(hipStream_t st, const Vp8lImg *imgs, int nimg, uint64_t max_pixels, const uint32_t *work, const uint32_t *hist, const Vp8lRefs &R) {
+    const unsigned max_chunks = unsigned((max_pixels + VP8L_CHUNK - 1) / VP8L_CHUNK);
+    CSH_LAUNCH(k_vp8l_parse, dim3(max_chunks, unsigned(nimg)), dim3(CSP_WAVE_THREADS), st, imgs, R.tok);
+    CSH_LAUNCH_PHASED(k_vp8l_refs_hist, 3, dim3(max_chunks, unsigned(nimg)), dim3(256), st, imgs, work, R.tok, R.hit, R.hist);
+    CSH_LAUNCH(k_vp8l_refs_codes, dim3(unsigned(nimg)), dim3(CSP_WAVE_THREADS), st, imgs, nimg, hist, R.hist, R.lens, R.pick);
+}
 void launch_vp8l_refs_packs(hipStream_t st, const Vp8lImg *imgs, int nimg, const uint32_t *work, const uint8_t *modes, const uint32_t *hist, const Vp8lRefs &R, uint8_t *out, uint32_t *file_len,
                             uint32_t *status) {
     CSH_LAUNCH(k_vp8l_pack_refs, dim3(unsigned(nimg)), dim3(CSP_WAVE_THREADS), st, imgs, nimg, work, modes, R.tok, R.hit, R.hist, R.lens, R.pick, out, file_len, status);

@@ -25,13 +25,15 @@ extern "C" int csl_encode_pixels(const csp_pixels *px, size_t count, int device,
     // the coder, read on every call: unset / empty / "plain" = literals only (the bytes oracle/png_oracle.c cso_vp8l_encode states), "refs" = backward
     // references and a colour cache (k_vp8l_refs.hip), "palette" = refs, and for a picture of at most 256 colours the colour-indexing transform where that is
     // smaller (k_vp8l_palette.hip), "groups" = palette, and for every picture of more than one tile its refs stream with a set of codes per group of tiles where that
-    // is smaller (k_vp8l_groups.hip)
+    // is smaller (k_vp8l_groups.hip), "far" = groups, and for every record a second token set from a match finder over the whole window where that is smaller
+    // (k_vp8l_far.hip)
     const char *mode = getenv("CSH_VP8L");
-    const bool groups = mode && !strcmp(mode, "groups");
+    const bool far = mode && !strcmp(mode, "far");
+    const bool groups = far || (mode && !strcmp(mode, "groups"));
     const bool palette = groups || (mode && !strcmp(mode, "palette"));
     const bool refs = palette || (mode && !strcmp(mode, "refs"));
     if (mode && *mode && !refs && strcmp(mode, "plain")) {
-        for (size_t i = 0; i < count; i++) results[i] = make_res(CS_ERR_UNSUPPORTED, "CSH_VP8L names no lossless WebP coder (plain, refs, palette, groups)");
+        for (size_t i = 0; i < count; i++) results[i] = make_res(CS_ERR_UNSUPPORTED, "CSH_VP8L names no lossless WebP coder (plain, refs, palette, groups, far)");
         return int(count);
     }
     int failed = 0;
@@ -74,6 +76,10 @@ extern "C" int csl_encode_pixels(const csp_pixels *px, size_t count, int device,
     DevBuf<csw::Vp8lGroupImg> d_gimg;
     DevBuf<uint32_t> d_feat, d_ghist;
     DevBuf<uint8_t> d_label, d_glens;
+    DevBuf<uint64_t> d_tok2;
+    DevBuf<uint32_t> d_pos0, d_pos1, d_prev, d_cnt, d_dtot, d_won, d_rhist2, d_pick2, d_feat2, d_ghist2;
+    DevBuf<uint8_t> d_lens2, d_label2, d_glens2;
+    DevBuf<unsigned long long> d_ginfo2;
     std::vector<uint32_t> len(imgs.size()), status(imgs.size());
     bool ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
     have_st = ok;
@@ -113,9 +119,9 @@ extern "C" int csl_encode_pixels(const csp_pixels *px, size_t count, int device,
              !d_lens.alloc(imgs.size() * csw::VP8L_LENS + 8) && !d_pick.alloc(imgs.size() * 4 + 4);
     // groups: the pictures' tiles (a picture of one tile has no grouped candidate) and the pools behind them, in this mode only
     uint32_t max_tiles = 0;
+    uint64_t tiles = 0;
     if (ok && groups) {
         std::vector<csw::Vp8lGroupImg> gimgs(nparent);
-        uint64_t tiles = 0;
         for (size_t k = 0; k < nparent; k++) {
             csw::Vp8lGroupImg &g = gimgs[k];
             const uint32_t b = csw::vp8l_group_bits(imgs[k].width, imgs[k].height);
@@ -128,9 +134,22 @@ extern "C" int csl_encode_pixels(const csp_pixels *px, size_t count, int device,
              !d_ghist.alloc(nparent * csw::VP8L_MAX_GROUPS * csw::VP8L_HIST + 8) && !d_ghist.zero(st) && !d_glens.alloc(nparent * csw::VP8L_MAX_GROUPS * csw::VP8L_LENS + 8) &&
              !d_ginfo.alloc(nparent * csw::VP8L_GROUP_INFO + 8) && !d_ginfo.zero(st);
     }
+    // far: the sort's two position arrays and the links (12 bytes per pixel), the digit counts (a word per 16 pixels), and a second set of every pool that depends
+    // on tokens (8 bytes per pixel and the per-record tables), in this mode only
+    if (ok && far)
+        ok = !d_pos0.alloc(work + 64) && !d_pos1.alloc(work + 64) && !d_prev.alloc(work + 64) && !d_cnt.alloc(cst / csw::VP8L_CACHE_STATE * 256 + 256) &&
+             !d_dtot.alloc(imgs.size() * csw::VP8L_FAR_TOT + 8) && !d_dtot.zero(st) && !d_won.alloc(imgs.size() + 1) && !d_tok2.alloc(work + 64) &&
+             !d_rhist2.alloc(imgs.size() * csw::VP8L_NOPT * csw::VP8L_HIST + 8) && !d_rhist2.zero(st) && !d_lens2.alloc(imgs.size() * csw::VP8L_LENS + 8) && !d_pick2.alloc(imgs.size() * 4 + 4) &&
+             !d_label2.alloc(tiles + 64) && !d_feat2.alloc(tiles * csw::VP8L_TILE_FEAT + 64) && !d_ghist2.alloc(nparent * csw::VP8L_MAX_GROUPS * csw::VP8L_HIST + 8) && !d_ghist2.zero(st) &&
+             !d_glens2.alloc(nparent * csw::VP8L_MAX_GROUPS * csw::VP8L_LENS + 8) && !d_ginfo2.alloc(nparent * csw::VP8L_GROUP_INFO + 8) && !d_ginfo2.zero(st);
     if (ok) {
         const csw::Vp8lRefs pools = {d_tok.p, d_hit.p, d_cst.p, d_rhist.p, d_lens.p, d_pick.p, d_gimg.p, d_label.p, d_feat.p, d_ghist.p, d_glens.p, d_ginfo.p};
-        if (groups)
+        if (far) {
+            const csw::Vp8lFar fp = {{d_pos0.p, d_pos1.p}, d_prev.p, d_cnt.p, d_dtot.p, d_won.p,
+                                     {d_tok2.p, d_hit.p, d_cst.p, d_rhist2.p, d_lens2.p, d_pick2.p, d_gimg.p, d_label2.p, d_feat2.p, d_ghist2.p, d_glens2.p, d_ginfo2.p}};
+            csw::launch_vp8l_encode_far(st, d_imgs.p, int(nparent), int(imgs.size() - nparent), max_blocks, max_px, max_packed, max_tiles, d_ptab.p, d_pal.p, d_work.p, d_modes.p, d_hist.p, pools, fp,
+                                        d_out.p, d_len.p, d_status.p);
+        } else if (groups)
             csw::launch_vp8l_encode_groups(st, d_imgs.p, int(nparent), int(imgs.size() - nparent), max_blocks, max_px, max_packed, max_tiles, d_ptab.p, d_pal.p, d_work.p, d_modes.p, d_hist.p,
                                            pools, d_out.p, d_len.p, d_status.p);
         else if (palette)

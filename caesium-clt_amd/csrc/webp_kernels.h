@@ -135,6 +135,35 @@ void launch_vp8l_pack_groups(hipStream_t st, const Vp8lImg *imgs, int nimg, cons
 // launch_vp8l_encode_palette with the group stages between the refs stages and the palette's choice; max_tiles: the largest Vp8lGroupImg::ntile
 void launch_vp8l_encode_groups(hipStream_t st, const Vp8lImg *imgs, int nparent, int ncand, uint32_t max_blocks, uint64_t max_pixels, uint64_t max_packed, uint32_t max_tiles,
                                const unsigned long long *tabs, uint32_t *pal, uint32_t *work, uint8_t *modes, uint32_t *hist, const Vp8lRefs &refs, uint8_t *out, uint32_t *file_len, uint32_t *status);
+// a match finder over the whole window (CSH_VP8L=far, k_vp8l_far.hip): everything CSH_VP8L=groups does, and for every record a second token set from a hash chain
+// over the whole record; the record keeps the set whose best stream is strictly smaller.  All of these pools exist in this mode only
+enum : uint32_t {
+    VP8L_FAR_LINKS = 8,                   // links walked per position
+    VP8L_FAR_BLOCK = VP8L_CHUNK,          // entries per block of the sort
+    VP8L_FAR_NONE = 0xFFFFFFFFu,          // prev: no link
+    VP8L_FAR_TOT = 3 * 256 + 8,           // per record: the digit totals of the three passes, then the number of positions with a link
+};
+struct Vp8lFar {
+    uint32_t *pos[2];      // the positions on their way through the sort, one u32 per pixel each (Vp8lImg::res_off)
+    uint32_t *prev;        // per pixel (res_off): the nearest earlier position with the same hash, or VP8L_FAR_NONE
+    uint32_t *cnt;         // per chunk of every record 256 digit counts: a record's are at 256 x (cst_off / VP8L_CACHE_STATE), digit-major
+    uint32_t *dtot;        // per record VP8L_FAR_TOT words, zeroed by the caller
+    uint32_t *won;         // per record: 1 where the second set replaced the first
+    Vp8lRefs B;            // the second set's pools; hit, cst and gimg are the first set's (they do not depend on tokens), hist / ghist / ginfo zeroed by the caller
+};
+// the chain of the records 0 .. nimg - 1 into far.prev; the second set's candidates into far.B.tok (k_vp8l_match's fixed distances, then the chain)
+void launch_vp8l_far_links(hipStream_t st, const Vp8lImg *imgs, int nimg, uint64_t max_pixels, const uint32_t *work, const Vp8lFar &far);
+void launch_vp8l_far_match(hipStream_t st, const Vp8lImg *imgs, int nimg, uint64_t max_pixels, const uint32_t *work, const Vp8lFar &far);
+// behind launch_vp8l_refs_stages and launch_vp8l_group_stages, in front of the palette's choice: the chain, the second set through the stages that depend on
+// tokens, the choice per record, and the second set's pools over the first's where it won
+void launch_vp8l_far_stages(hipStream_t st, const Vp8lImg *imgs, int nparent, int nimg, uint64_t max_pixels, uint32_t max_tiles, const uint32_t *work, const uint32_t *hist, const Vp8lRefs &refs,
+                            const Vp8lFar &far);
+// the stages of launch_vp8l_refs_stages that depend on tokens, over refs.tok as a match finder left it: the parse, the counts, the codes and pick (k_vp8l_refs.hip)
+void launch_vp8l_token_stages(hipStream_t st, const Vp8lImg *imgs, int nimg, uint64_t max_pixels, const uint32_t *work, const uint32_t *hist, const Vp8lRefs &refs);
+// launch_vp8l_encode_groups with launch_vp8l_far_stages in it
+void launch_vp8l_encode_far(hipStream_t st, const Vp8lImg *imgs, int nparent, int ncand, uint32_t max_blocks, uint64_t max_pixels, uint64_t max_packed, uint32_t max_tiles,
+                            const unsigned long long *tabs, uint32_t *pal, uint32_t *work, uint8_t *modes, uint32_t *hist, const Vp8lRefs &refs, const Vp8lFar &far, uint8_t *out, uint32_t *file_len,
+                            uint32_t *status);
 // pieces of launch_vp8l_encode (k_vp8l_enc.hip) the refs coder runs as they are: the front end, and the plain pack for the pictures whose pick[4 i] is 0 (pick = nullptr: all)
 void launch_vp8l_front(hipStream_t st, const Vp8lImg *imgs, int nimg, uint32_t max_blocks, uint64_t max_pixels, uint32_t *work, uint8_t *modes, uint32_t *hist);
 void launch_vp8l_pack_plain(hipStream_t st, const Vp8lImg *imgs, int nimg, const uint32_t *work, const uint8_t *modes, const uint32_t *hist, const uint32_t *pick, uint8_t *out, uint32_t *file_len,

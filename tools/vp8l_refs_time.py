@@ -1,12 +1,13 @@
 """Time csl_encode_pixels (pixels in device memory -> lossless WebP files) in its coders, in one process: CSH_VP8L=plain (literals only), CSH_VP8L=refs
 (backward references and a colour cache), CSH_VP8L=palette (refs, and the colour-indexing transform for pictures of at most 256 colours), CSH_VP8L=groups
-(palette, and an entropy image of up to eight groups of prefix codes).  96 pictures of
-1920 x 1080 by default: photographic (three textures) and graphic content, repeated.
+(palette, and an entropy image of up to eight groups of prefix codes), CSH_VP8L=far (groups, and a second token set from a match finder over the whole window).
+96 pictures of 1920 x 1080 by default: photographic (three textures) and graphic content, repeated.
 
-    python tools/vp8l_refs_time.py [--count 96] [--width 1920] [--height 1080] [--repeats 3] [--once] [--modes plain,refs] [--dithered 0]
+    python tools/vp8l_refs_time.py [--count 96] [--width 1920] [--height 1080] [--repeats 3] [--once] [--modes plain,refs] [--dithered 0] [--library PATH]
 
 --once: one call per mode after the warm-up (what a kernel trace wants); --modes: the coders to run, the first is what the others are compared with;
---dithered K: K more pictures, texture 5 dithered to 16 colours (Floyd-Steinberg), behind the mix.  Prints one line per call and a summary."""
+--dithered K: K more pictures, texture 5 dithered to 16 colours (Floyd-Steinberg), behind the mix; --library: another build of libcaesium_hip.so (the parent commit's, to compare a mode across commits: `--modes groups,far` in one process gives far
+against groups).  Prints one line per call and a summary."""
 import argparse
 import ctypes as C
 import os
@@ -47,9 +48,10 @@ def main():
     ap.add_argument("--once", action="store_true")
     ap.add_argument("--modes", default="plain,refs")
     ap.add_argument("--dithered", type=int, default=0)
+    ap.add_argument("--library", default=None)
     a = ap.parse_args()
     pkg = package()
-    api = pkg.load()
+    api = pkg.CaesiumHip(a.library) if a.library else pkg.load()
     assert api.device_count() >= 1, "no HIP device"
     from caesium_clt_amd.binding import CByteArray, CCSResult
     base = [torch.from_numpy(np.ascontiguousarray(p)).cuda() for p in pictures(a.width, a.height)]
