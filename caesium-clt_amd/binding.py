@@ -49,7 +49,7 @@ EXPORTS = ["cs_default_parameters", "cs_compress_in_memory", "cs_compress_to_siz
            "csh_batch_run", "csh_batch_fetch", "csh_batch_destroy", "csh_batch_retain_dct", "csh_batch_set_quality", "csh_batch_rerun_encode", "cs_batch_compress_to_size", "csh_batch_geometry", "csh_batch_read_coefs",
            "csp_kernel_name", "csp_batch_create", "csp_batch_create_webp", "csp_batch_create_pixels", "csh_batch_create_pixels", "csh_batch_pixels", "csh_batch_create_from_pixels", "csp_png_to_jpeg", "csp_png_to_lossless_webp", "csp_batch_run", "csp_batch_fetch", "csp_batch_destroy", "csp_batch_geometry", "csp_batch_read_rows", "csp_batch_read_stream",
            "csp_batch_trials", "csp_batch_read_scores", "csp_batch_chunk_bits", "csh_batch_create_webp", "cs_batch_convert",
-           "cswd_batch_create", "cswd_batch_run", "cswd_batch_pixels", "cswd_batch_read_pixels", "cswd_batch_alpha", "cswd_batch_read_rgba", "cswd_batch_destroy", "cswd_rgba_join", "cswd_rgba_destroy", "csh_batch_create_webp_from_pixels", "csh_batch_create_from_pixels_rgb", "csl_encode_pixels", "csl_attach_alpha"]
+           "cswd_batch_create", "cswd_batch_run", "cswd_batch_pixels", "cswd_batch_read_pixels", "cswd_batch_alpha", "cswd_batch_read_rgba", "cswd_batch_destroy", "cswd_batch_frames", "cswd_batch_read_canvas", "cswd_batch_encode_anim", "cswd_rgba_join", "cswd_rgba_destroy", "csh_batch_create_webp_from_pixels", "csh_batch_create_from_pixels_rgb", "csl_encode_pixels", "csl_attach_alpha"]
 
 
 def _declare(L):
@@ -108,6 +108,9 @@ def _declare(L):
     L.cswd_batch_read_rgba.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
     L.cswd_batch_destroy.argtypes = [C.c_void_p]
     L.cswd_batch_destroy.restype = None
+    L.cswd_batch_frames.argtypes = [C.c_void_p, C.c_size_t, P(C.c_uint32), P(C.c_uint32), P(C.c_uint32)]
+    L.cswd_batch_read_canvas.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
+    L.cswd_batch_encode_anim.argtypes = [C.c_void_p, P(CByteArray), P(C.c_size_t), C.c_size_t, P(CCSParameters), C.c_int, P(CByteArray), P(CCSResult)]
     L.cswd_rgba_join.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.cswd_rgba_join.restype = C.c_int
     L.cswd_rgba_destroy.argtypes = [C.c_void_p]
@@ -399,6 +402,42 @@ class CaesiumHip:
                 a = np.empty((hh.value, w.value, 4 if rgba.value else 3), dtype=np.uint8)   # a picture with transparency comes back as RGBA
                 if (L.cswd_batch_read_rgba if rgba.value else L.cswd_batch_read_pixels)(h, i, a.ctypes.data):
                     raise CaesiumError(-1, L.csh_last_error().decode())
+                out.append(a)
+            return out
+        finally:
+            L.cswd_batch_destroy(h)
+
+    def webp_anim_canvases(self, blobs, device=0):
+        """animated WebP files -> per file an array [frames][H][W][4] uint8: every canvas as libwebp's AnimDecoder composes it (blend and dispose applied),
+        rebuilt on the device from the decoded frames; a CaesiumError per file that fails, or that is a still picture"""
+        import numpy as np
+        L = self.L
+        n = len(blobs)
+        keep = [C.create_string_buffer(x, len(x)) for x in blobs]
+        ins = (CByteArray * n)()
+        for i, buf in enumerate(keep):
+            ins[i].data = C.cast(buf, C.POINTER(C.c_uint8)); ins[i].length = len(blobs[i])
+        h = C.c_void_p()
+        rc = L.cswd_batch_create(ins, n, device, C.byref(h))
+        if rc:
+            raise CaesiumError(rc, L.csh_last_error().decode())
+        try:
+            rc = L.cswd_batch_run(h)
+            if rc:
+                raise CaesiumError(rc, L.csh_last_error().decode())
+            out = []
+            for i in range(n):
+                nf = C.c_uint32(); w = C.c_uint32(); hh = C.c_uint32()
+                rc = L.cswd_batch_frames(h, i, C.byref(nf), C.byref(w), C.byref(hh))
+                if rc or not nf.value:
+                    p = C.c_void_p(); ch = C.c_uint32(); msg = C.c_char_p()
+                    rc = L.cswd_batch_pixels(h, i, C.byref(p), C.byref(w), C.byref(hh), C.byref(ch), C.byref(msg))
+                    out.append(CaesiumError(rc or 10201, (msg.value or b"").decode() if rc else "not an animated WebP file"))
+                    continue
+                a = np.empty((nf.value, hh.value, w.value, 4), dtype=np.uint8)
+                for k in range(nf.value):
+                    if L.cswd_batch_read_canvas(h, i, k, a[k].ctypes.data):
+                        raise CaesiumError(-1, L.csh_last_error().decode())
                 out.append(a)
             return out
         finally:

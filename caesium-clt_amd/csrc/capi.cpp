@@ -39,7 +39,22 @@ enum { CS_GROUP = 2048 };
 static uint64_t webp_declared_pixels(const uint8_t *d, size_t n) {
     if (n < 30 || memcmp(d, "RIFF", 4) || memcmp(d + 8, "WEBP", 4)) return 0;
     const uint8_t *f = d + 20;
-    if (!memcmp(d + 12, "VP8X", 4)) return (uint64_t(f[4] | (f[5] << 8) | (f[6] << 16)) + 1) * (uint64_t(f[7] | (f[8] << 8) | (f[9] << 16)) + 1);
+    if (!memcmp(d + 12, "VP8X", 4)) {
+        const uint64_t canvas = (uint64_t(f[4] | (f[5] << 8) | (f[6] << 16)) + 1) * (uint64_t(f[7] | (f[8] << 8) | (f[9] << 16)) + 1);
+        if (!(f[0] & 0x02)) return canvas;
+        // an animated file: every ANMF frame is a picture of its own on the device (its 24-bit width - 1 / height - 1 at bytes 6 and 9 of the chunk), so the frames
+        // count, not the canvas
+        uint64_t frames = 0;
+        for (size_t i = 12; i + 8 <= n;) {
+            const size_t cl = size_t(d[i + 4]) | (size_t(d[i + 5]) << 8) | (size_t(d[i + 6]) << 16) | (size_t(d[i + 7]) << 24);
+            if (!memcmp(d + i, "ANMF", 4) && i + 8 + 16 <= n) {
+                const uint8_t *a = d + i + 8;
+                frames += (uint64_t(a[6] | (a[7] << 8) | (a[8] << 16)) + 1) * (uint64_t(a[9] | (a[10] << 8) | (a[11] << 16)) + 1);
+            }
+            i += 8 + cl + (cl & 1);
+        }
+        return std::max(canvas, frames);
+    }
     if (!memcmp(d + 12, "VP8 ", 4)) return (f[3] == 0x9D && f[4] == 0x01 && f[5] == 0x2A) ? uint64_t((f[6] | (f[7] << 8)) & 0x3FFF) * uint64_t((f[8] | (f[9] << 8)) & 0x3FFF) : 0;
     if (!memcmp(d + 12, "VP8L", 4) && f[0] == 0x2F) { const uint32_t b = uint32_t(f[1]) | (uint32_t(f[2]) << 8) | (uint32_t(f[3]) << 16) | (uint32_t(f[4]) << 24); return uint64_t((b & 0x3FFF) + 1) * uint64_t(((b >> 14) & 0x3FFF) + 1); }
     return 0;
@@ -241,7 +256,10 @@ static int webp_inputs(const CByteArray *inputs, size_t count, const CCSParamete
     // groups by what the decoder reserves, not by file bytes: per declared pixel 3 B of RGB, 5 B of alpha room and 8 B of VP8L work area
     // (+ 4 MiB + 16 x the file), so ~20 B per pixel of the canvas the header declares -- a tiny file may declare 16383 x 16383.  A group
     // that still fails for want of memory is halved and tried again (as the JPEG row does), so that one oversized header fails alone.
+    // An animated file counts every frame (webp_declared_pixels): its frames are pictures of the batch, coded again by cswd_batch_encode_anim below -- for target
+    // WebP without a size; an animation whose frames alone exceed the cap is refused before anything is reserved for it.
     const uint64_t pool_cap = uint64_t(64) << 30;
+    auto animated = [](const CByteArray &in) { return in.length >= 30 && !memcmp(in.data, "RIFF", 4) && !memcmp(in.data + 8, "WEBPVP8X", 8) && (in.data[20] & 0x02); };
     size_t limit = 512;
     for (size_t g0 = 0, n = 0; g0 < count; g0 += n) {
         uint64_t bytes = 0, pools = 0;
@@ -251,6 +269,11 @@ static int webp_inputs(const CByteArray *inputs, size_t count, const CCSParamete
             bytes += inputs[g0 + n].length; pools += est;
         }
         for (size_t k = 0; k < n; k++) { outputs[g0 + k].data = nullptr; outputs[g0 + k].length = 0; }
+        if (n == 1 && pools > pool_cap && animated(inputs[g0])) {
+            if (results) results[g0] = make_result(CS_ERR_UNSUPPORTED, "animated WebP: the frames of this file exceed the device pools of one batch");
+            failed_total++;
+            continue;
+        }
         cswd_batch *wb = nullptr;
         int rc = cswd_batch_create(inputs + g0, n, device, &wb);
         if (rc == 0) rc = cswd_batch_run(wb);
@@ -264,8 +287,16 @@ static int webp_inputs(const CByteArray *inputs, size_t count, const CCSParamete
         std::vector<const uint8_t *> aplane;   // per picture: its alpha plane in device memory, or null (opaque)
         std::vector<csp_pixels> rgb3;          // per picture: its RGB whatever its transparency ...
         std::vector<const uint8_t *> rplane;   // ... and the plane of a picture the RGBA consumers (PNG, lossless WebP) get: what a resize works on
-        std::vector<size_t> at;
+        std::vector<size_t> at, anim_at;       // anim_at: the animated files of the group (indices into it)
         for (size_t k = 0; k < n && rc == 0; k++) {
+            uint32_t nframes = 0, cw = 0, ch = 0;
+            if (!cswd_batch_frames(wb, k, &nframes, &cw, &ch) && nframes) {   // an animated file: its own path, for WebP output at the canvas' size
+                const char *why = target != CS_TYPE_WEBP ? "an animated WebP file converts to no JPEG / PNG in this build (it is compressed as animated WebP)"
+                                  : (p->width || p->height) ? "resizing an animated WebP file has no path in this build" : nullptr;
+                if (!why) anim_at.push_back(k);
+                else { if (results) results[g0 + k] = make_result(CS_ERR_UNSUPPORTED, why); failed_total++; }
+                continue;
+            }
             csp_pixels s; const char *msg = "";
             int code = cswd_batch_pixels(wb, k, &s.device_pixels, &s.width, &s.height, &s.channels, &msg);
             const uint8_t *rgba = nullptr, *plane = nullptr;
@@ -357,6 +388,11 @@ static int webp_inputs(const CByteArray *inputs, size_t count, const CCSParamete
             }
             csp_batch_destroy(pb); csh_batch_destroy(jb); csh_batch_destroy(rb); csh_batch_destroy(rb2);
             for (cswd_rgba *jn : joined) cswd_rgba_destroy(jn);
+        }
+        if (!anim_at.empty()) {
+            std::vector<CCSResult> res(n);
+            failed_total += cswd_batch_encode_anim(wb, inputs + g0, anim_at.data(), anim_at.size(), p, device, outputs + g0, res.data());
+            for (size_t k : anim_at) { if (results) results[g0 + k] = res[k]; else cs_free_result(&res[k]); }
         }
         cswd_batch_destroy(wb);
     }

@@ -3,7 +3,7 @@
 // webp::compress and convert_in_memory do with libwebp's decoder in front (/root/reference/src/compressor.rs:289-305).
 // Built: lossy (VP8) and lossless (VP8L) still pictures, with or without transparency (an ALPH chunk next to the VP8 frame, or a VP8L picture that is
 // not opaque): such a picture leaves its RGB, its RGBA and its alpha plane in HBM (cswd_batch_alpha), and the caller picks what its encoder takes.
-// Animation answers CS_ERR_UNSUPPORTED per file.
+// An animated file (ANIM / ANMF chunks) becomes a range of pictures, one per frame: webp_anim.cpp.
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -11,30 +11,28 @@
 #include <vector>
 
 #include "../../include/caesium_hip.h"
-#include "devmem.hpp"
-#include "webp_kernels.h"
-#include "vp8_dec.h"
+#include "webp_anim.hpp"
 #include "vp8l_dec.h"
 
 using namespace csh;
 
-struct cswd_batch {
-    int device = 0;
-    hipStream_t stream = 0;
-    bool have_stream = false;
-    struct Item { int code = 0; std::string msg; int image = -1; };
-    std::vector<Item> items;
-    std::vector<csw::Vp8In> imgs;
-    std::vector<uint8_t> pool;
-    DevBuf<uint8_t> d_pool, d_work, d_rgb;
-    DevBuf<csw::Vp8In> d_imgs;
-    uint64_t work_bytes = 0, rgb_bytes = 0;
-    bool ran = false;
-    ~cswd_batch() { if (have_stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); } }   // nothing queued may outlive the device blocks
-};
-
 static uint32_t rd32le(const uint8_t *d) { return uint32_t(d[0]) | (uint32_t(d[1]) << 8) | (uint32_t(d[2]) << 16) | (uint32_t(d[3]) << 24); }
 
+enum { PARSE_ANIMATED = -2 };   // parse_webp: the file has ANIM / ANMF chunks (cswd_parse_anim takes it)
+// what a VP8 key frame / a VP8L stream says its size is
+static int frame_size(const uint8_t *f, size_t len, bool lossless, uint32_t &w, uint32_t &h, std::string &msg) {
+    if (len < (lossless ? 5u : 10u)) { msg = "no VP8 frame in the WebP file"; return CS_ERR_BAD_WEBP; }
+    if (lossless) {   // signature, 14 + 14 bits of size minus one, alpha hint, version
+        const uint32_t bits = rd32le(f + 1);
+        if (f[0] != 0x2F || (bits >> 29) != 0) { msg = "malformed VP8L header"; return CS_ERR_BAD_WEBP; }
+        w = (bits & 0x3FFFu) + 1; h = ((bits >> 14) & 0x3FFFu) + 1;
+        return 0;
+    }
+    if ((f[0] & 1) || f[3] != 0x9D || f[4] != 0x01 || f[5] != 0x2A) { msg = "malformed VP8 frame header"; return CS_ERR_BAD_WEBP; }
+    w = (uint32_t(f[6]) | (uint32_t(f[7]) << 8)) & 0x3FFF; h = (uint32_t(f[8]) | (uint32_t(f[9]) << 8)) & 0x3FFF;
+    if (!w || !h) { msg = "empty VP8 frame"; return CS_ERR_BAD_WEBP; }
+    return 0;
+}
 // RIFF walk: where the VP8 key frame lies; refuses what this build does not decode
 static int parse_webp(const uint8_t *d, size_t n, size_t &off, size_t &len, uint32_t &w, uint32_t &h, bool &lossless, size_t &alph_off, size_t &alph_len, std::string &msg) {
     lossless = false; alph_off = 0; alph_len = 0;
@@ -48,22 +46,12 @@ static int parse_webp(const uint8_t *d, size_t n, size_t &off, size_t &len, uint
         if (!memcmp(d + i, "VP8 ", 4)) { if (!found) { off = i + 8; len = cl; found = true; } }
         else if (!memcmp(d + i, "VP8L", 4)) { if (!found) { off = i + 8; len = cl; found = true; lossless = true; } }
         else if (!memcmp(d + i, "ALPH", 4)) { if (!found && !alph_len) { alph_off = i + 8; alph_len = cl; } }   // the alpha plane of the VP8 frame that follows
-        else if (!memcmp(d + i, "ANIM", 4) || !memcmp(d + i, "ANMF", 4)) { msg = "animated WebP input has no device path in this build"; return CS_ERR_UNSUPPORTED; }
+        else if (!memcmp(d + i, "ANIM", 4) || !memcmp(d + i, "ANMF", 4)) return PARSE_ANIMATED;
         i += 8 + cl + (cl & 1);
     }
-    if (!found || len < (lossless ? 5u : 10u)) { msg = "no VP8 frame in the WebP file"; return CS_ERR_BAD_WEBP; }
-    const uint8_t *f = d + off;
+    if (!found) { msg = "no VP8 frame in the WebP file"; return CS_ERR_BAD_WEBP; }
     if (lossless) alph_len = 0;
-    if (lossless) {   // signature, 14 + 14 bits of size minus one, alpha hint, version
-        const uint32_t bits = rd32le(f + 1);
-        if (f[0] != 0x2F || (bits >> 29) != 0) { msg = "malformed VP8L header"; return CS_ERR_BAD_WEBP; }
-        w = (bits & 0x3FFFu) + 1; h = ((bits >> 14) & 0x3FFFu) + 1;
-        return 0;
-    }
-    if ((f[0] & 1) || f[3] != 0x9D || f[4] != 0x01 || f[5] != 0x2A) { msg = "malformed VP8 frame header"; return CS_ERR_BAD_WEBP; }
-    w = (uint32_t(f[6]) | (uint32_t(f[7]) << 8)) & 0x3FFF; h = (uint32_t(f[8]) | (uint32_t(f[9]) << 8)) & 0x3FFF;
-    if (!w || !h) { msg = "empty VP8 frame"; return CS_ERR_BAD_WEBP; }
-    return 0;
+    return frame_size(d + off, len, lossless, w, h, msg);
 }
 
 extern "C" int cswd_batch_create(const CByteArray *inputs, size_t count, int device, cswd_batch **out) {
@@ -75,18 +63,12 @@ extern "C" int cswd_batch_create(const CByteArray *inputs, size_t count, int dev
     if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) { csh_set_error("hipStreamCreate failed"); return CS_ERR_NO_DEVICE; }
     b->have_stream = true;
     b->items.resize(count);
-    for (size_t n = 0; n < count; n++) {
-        cswd_batch::Item &it = b->items[n];
-        size_t off = 0, len = 0;
-        uint32_t w = 0, h = 0;
-        bool lossless = false;
-        size_t alph_off = 0, alph_len = 0;
-        it.code = parse_webp(inputs[n].data, inputs[n].length, off, len, w, h, lossless, alph_off, alph_len, it.msg);
-        if (it.code) continue;
+    // one more picture of the batch: a still file's frame, or a frame of an animated file
+    auto add_image = [&](const uint8_t *d, size_t off, size_t len, uint32_t w, uint32_t h, bool lossless, size_t alph_off, size_t alph_len) -> int {
         csw::Vp8In im;
         memset(&im, 0, sizeof im);
         im.data_off = b->pool.size(); im.data_len = uint32_t(len);
-        b->pool.insert(b->pool.end(), inputs[n].data + off, inputs[n].data + off + len);
+        b->pool.insert(b->pool.end(), d + off, d + off + len);
         b->pool.resize((b->pool.size() + 15) & ~size_t(15));
         im.width = w; im.height = h; im.mbw = (w + 15) / 16; im.mbh = (h + 15) / 16;
         im.lossless = lossless ? 1u : 0u;
@@ -94,7 +76,7 @@ extern "C" int cswd_batch_create(const CByteArray *inputs, size_t count, int dev
         uint64_t work = lossless ? csw::vp8l_work_bytes(w, h, len) : csw::vp8_work_bytes(im.mbw, im.mbh);
         if (alph_len) {
             im.alph_off = b->pool.size(); im.alph_len = uint32_t(alph_len);
-            b->pool.insert(b->pool.end(), inputs[n].data + alph_off, inputs[n].data + alph_off + alph_len);
+            b->pool.insert(b->pool.end(), d + alph_off, d + alph_off + alph_len);
             b->pool.resize((b->pool.size() + 15) & ~size_t(15));
             work = std::max(work, csw::vp8l_work_bytes(w, h, alph_len));   // the plane's VP8L stream is decoded in the frame's work area, after the frame
         }
@@ -105,8 +87,34 @@ extern "C" int cswd_batch_create(const CByteArray *inputs, size_t count, int dev
             im.rgba_off = b->rgb_bytes; b->rgb_bytes += (uint64_t(w) * h * 4 + 63) & ~uint64_t(63);
             im.a_off = b->rgb_bytes; b->rgb_bytes += (uint64_t(w) * h + 63) & ~uint64_t(63);
         }
-        it.image = int(b->imgs.size());
         b->imgs.push_back(im);
+        return int(b->imgs.size()) - 1;
+    };
+    for (size_t n = 0; n < count; n++) {
+        cswd_batch::Item &it = b->items[n];
+        size_t off = 0, len = 0;
+        uint32_t w = 0, h = 0;
+        bool lossless = false;
+        size_t alph_off = 0, alph_len = 0;
+        it.code = parse_webp(inputs[n].data, inputs[n].length, off, len, w, h, lossless, alph_off, alph_len, it.msg);
+        if (it.code == PARSE_ANIMATED) {   // every ANMF frame is one more picture; the file keeps the range
+            cswd_anim a;
+            std::vector<cswd_frame_src> src;
+            it.code = cswd_parse_anim(inputs[n].data, inputs[n].length, a, src, it.msg);
+            for (size_t k = 0; k < src.size() && !it.code; k++) {   // a frame's bitstream has to say the size its ANMF header says
+                uint32_t fw = 0, fh = 0;
+                it.code = frame_size(inputs[n].data + src[k].off, src[k].len, src[k].lossless, fw, fh, it.msg);
+                if (!it.code && (fw != a.frames[k].w || fh != a.frames[k].h)) { it.code = CS_ERR_BAD_WEBP; it.msg = "an animation frame's bitstream and its ANMF header disagree about its size"; }
+            }
+            if (it.code) continue;
+            for (size_t k = 0; k < src.size(); k++)
+                a.frames[k].image = uint32_t(add_image(inputs[n].data, src[k].off, src[k].len, a.frames[k].w, a.frames[k].h, src[k].lossless, src[k].lossless ? 0 : src[k].alph_off, src[k].lossless ? 0 : src[k].alph_len));
+            it.anim = int(b->anims.size());
+            b->anims.push_back(std::move(a));
+            continue;
+        }
+        if (it.code) continue;
+        it.image = add_image(inputs[n].data, off, len, w, h, lossless, alph_off, alph_len);
     }
     if (!b->imgs.empty()) {
         if (b->d_pool.upload(b->pool, b->stream) || b->d_imgs.upload(b->imgs, b->stream) || b->d_work.alloc(b->work_bytes + 64) || b->d_rgb.alloc(b->rgb_bytes + 64)) return CS_ERR_NO_DEVICE;
@@ -136,6 +144,10 @@ extern "C" int cswd_batch_run(cswd_batch *b) {
             it.code = st >= 2 ? CS_ERR_UNSUPPORTED : CS_ERR_BAD_WEBP;
             it.msg = st == 3 ? "WebP input with transparency: no room was reserved for its alpha" : st == 2 ? "WebP frame beyond this build (frame type / prefix-code work area)" : "malformed WebP stream";
         }
+    for (cswd_batch::Item &it : b->items)   // an animated file fails as a whole when one of its frames does
+        if (it.anim >= 0)
+            for (const csw::AnimFrame &f : b->anims[size_t(it.anim)].frames)
+                if (b->imgs[f.image].status) { it.code = CS_ERR_BAD_WEBP; it.msg = "malformed WebP stream in a frame of the animation"; break; }
     b->ran = true;
     return 0;
 }
@@ -145,6 +157,7 @@ extern "C" int cswd_batch_pixels(cswd_batch *b, size_t image, const uint8_t **de
     const cswd_batch::Item &it = b->items[image];
     if (message) *message = it.msg.c_str();
     if (it.code) return it.code;
+    if (it.anim >= 0) { if (message) *message = "an animated WebP file is not one picture (cswd_batch_frames, cswd_batch_encode_anim)"; return CS_ERR_UNSUPPORTED; }
     const csw::Vp8In &im = b->imgs[size_t(it.image)];
     *device_pixels = b->d_rgb.p + im.rgb_off; *width = im.width; *height = im.height; *channels = 3;
     return 0;
@@ -156,6 +169,7 @@ extern "C" int cswd_batch_alpha(cswd_batch *b, size_t image, const uint8_t **dev
     if (!b->ran || image >= b->items.size()) { csh_set_error("cswd_batch_alpha: batch not run / index out of range"); return -1; }
     const cswd_batch::Item &it = b->items[image];
     if (it.code) return it.code;
+    if (it.anim >= 0) return CS_ERR_UNSUPPORTED;
     const csw::Vp8In &im = b->imgs[size_t(it.image)];
     if (im.has_alpha) { *device_rgba = b->d_rgb.p + im.rgba_off; *device_alpha = b->d_rgb.p + im.a_off; }
     return 0;

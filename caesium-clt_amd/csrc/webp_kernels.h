@@ -174,4 +174,31 @@ struct Vp8In;
 void launch_vp8_decode(hipStream_t st, const uint8_t *pool, Vp8In *imgs, int n, uint8_t *work, uint8_t *rgb, int nsteps, int psteps_lossless, int psteps_alpha);
 void launch_rgba_join(hipStream_t st, const uint8_t *rgb, const uint8_t *alpha, uint8_t *rgba, uint64_t npx);
 
+// animated WebP inputs (k_webp_anim.hip): the canvases of a file rebuilt from its decoded frames (libwebp's AnimDecoder: blend and dispose), and what changed
+// from one canvas to the next.  Every frame is a picture of the decode batch; a lane owns a canvas pixel and walks the file's frames in order
+enum : uint32_t {
+    ANIM_DISPOSE = 1,      // AnimFrame::flags: the frame's rectangle is cleared before the next frame (ANMF bit 0)
+    ANIM_NO_BLEND = 2,     // the frame replaces what is under it (ANMF bit 1)
+    ANIM_KEY = 4,          // set by the host: the canvas is cleared in front of this frame and the frame copied in (anim_key_frames)
+    ANIM_HOLES = 8,        // output: the rectangle is written in blend form, an unchanged pixel as 0x00000000
+};
+enum : uint32_t { ANIM_STAT = 8 };   // words per frame of the statistics
+struct AnimFrame {
+    uint32_t image;        // the frame's picture: its Vp8In record
+    uint32_t x, y, w, h;   // where it lies on the canvas
+    uint32_t flags;
+    // the frame as it is written again, set by the host between the two walks
+    uint32_t ox, oy, ow, oh;
+    uint32_t split;        // 1: RGB (3 bytes per pixel) at out_off and the alpha plane at a_off, for the lossy encoder; 0: RGBA at out_off
+    uint64_t out_off, a_off;   // in the rectangle pool
+};
+struct AnimFile { uint32_t first, nframes, cw, ch; };   // a file's frames in the frame array, its canvas
+// statistics of frame k against canvas k - 1, ANIM_STAT words: the bounding box of the changed pixels (min x, min y, max x, max y; the minima start at ~0),
+// how many pixels changed, how many of those are not opaque; word 6 (the pack walk): 1 where the written rectangle holds an alpha below 255
+enum { ANIM_WALK_STATS = 0, ANIM_WALK_PACK = 1, ANIM_WALK_CANVAS = 2 };
+// mode ANIM_WALK_STATS: the statistics; ANIM_WALK_PACK: every frame's output rectangle into `pool`; ANIM_WALK_CANVAS: canvas `frame` of the one file given,
+// as RGBA, into `pool`.  max_px: the largest canvas of the files, in pixels
+void launch_webp_anim(hipStream_t st, int mode, const AnimFile *files, int nfiles, uint64_t max_px, const AnimFrame *frames, const Vp8In *imgs, const uint8_t *rgb, uint32_t *stats, uint8_t *pool,
+                      uint32_t frame);
+
 }  // namespace csw

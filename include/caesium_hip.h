@@ -239,7 +239,8 @@ int csp_batch_chunk_bits(csp_batch *b, size_t image, int trial, uint64_t *dst, s
  * WebP INPUTS (libcaesium decodes them with libwebp before webp::compress / convert_in_memory, compressor.rs:289-305): the RIFF
  * container is walked on the host, the VP8 key frame is decoded on the device (k_webp_dec.hip), the RGB stays in HBM
  * (cswd_batch_pixels: the csp_pixels the encoders take).  Built: lossy (VP8) and lossless (VP8L) still pictures, transparency (ALPH chunk, non-opaque
- * VP8L) included -- cswd_batch_alpha; animation answers CS_ERR_UNSUPPORTED per file.  cs_batch_compress and cs_batch_convert route WebP files here themselves.
+ * VP8L) included -- cswd_batch_alpha.  An animated file (ANIM / ANMF chunks) is a range of pictures of the batch, one per frame: cswd_batch_frames,
+ * cswd_batch_encode_anim; cswd_batch_pixels answers CS_ERR_UNSUPPORTED for it.  cs_batch_compress and cs_batch_convert route WebP files here themselves.
  */
 /* lossless WebP OUTPUT (webp.lossless; libcaesium: webp::compress with libwebp's lossless coder, compressor.rs:427-429, 289-305):
  * 8-bit grey (channels 1), grey + alpha (2), RGB (3) or RGBA (4) pictures that are in device memory -> one VP8L file each (k_vp8l_enc.hip).
@@ -265,6 +266,15 @@ int cswd_batch_read_pixels(cswd_batch *b, size_t image, uint8_t *dst /* width * 
 int cswd_batch_alpha(cswd_batch *b, size_t image, const uint8_t **device_rgba, const uint8_t **device_alpha);
 int cswd_batch_read_rgba(cswd_batch *b, size_t image, uint8_t *dst /* width * height * 4; returns 1 for an opaque picture */);
 void cswd_batch_destroy(cswd_batch *b);
+/* animated files.  cswd_batch_frames: the file's code if it failed, else 0 with *nframes = 0 for a still picture, or the frame count and the canvas of an
+   animated one.  cswd_batch_read_canvas (after cswd_batch_run): canvas `frame` as libwebp's AnimDecoder composes it (blend and dispose applied), canvas_w *
+   canvas_h * 4 bytes of RGBA; the canvas is rebuilt on the device for the call and kept nowhere.
+   cswd_batch_encode_anim: files[0 .. nfiles - 1] (indices of animated files of the batch; sources = the array the batch was created from) coded again as animated
+   WebP at p->webp_quality, or losslessly under p->webp_lossless: same canvas, frame count, durations, loop count and background colour; frame 0 whole, every later
+   frame the bounding box of what changed (left and top edge even).  outputs / results are indexed like sources; returns the number of failed files */
+int cswd_batch_frames(cswd_batch *b, size_t file, uint32_t *nframes, uint32_t *canvas_w, uint32_t *canvas_h);
+int cswd_batch_read_canvas(cswd_batch *b, size_t file, uint32_t frame, uint8_t *dst_rgba);
+int cswd_batch_encode_anim(cswd_batch *b, const CByteArray *sources, const size_t *files, size_t nfiles, const CCSParameters *p, int device, CByteArray *outputs, CCSResult *results);
 /* the two halves of a picture with transparency after their resize (RGB, 3 bytes per pixel, and the alpha plane, both in device memory) joined into one
    RGBA picture in device memory of its own: what the PNG coder and the lossless WebP coder take (image-rs resamples the four channels alike,
    /root/reference/src/compressor.rs:289-300 through libcaesium's resize).  0 ok. */
