@@ -177,6 +177,10 @@ static int plan_item(Item &it, const CCSParameters &p, bool lossless) {
         if (o.width > 65500 || o.height > 65500 || uint64_t(o.width) * uint64_t(o.height) > (1ull << 28)) { it.msg = "resize target too large for JPEG"; return CS_ERR_JPEG_FEATURE; }
     }
     if (lossless) {
+        // the output carries the slots as the file leaves them (frame_header): a component decoded with other contents cannot be
+        // transcoded (libjpeg jpeg_copy_critical_parameters: JERR_MISMATCHED_QUANT_TABLE)
+        for (int c = 0; c < in.ncomp; c++)
+            if (memcmp(in.comp[c].qt, in.qt[in.comp[c].tq], sizeof in.comp[c].qt)) { it.msg = "a component was decoded with a quantisation table that its slot no longer holds"; return CS_ERR_JPEG_FEATURE; }
         for (int c = 0; c < in.ncomp; c++) o.comp[c] = in.comp[c];
         jpeg_geometry(o);
         return 0;
@@ -519,7 +523,7 @@ void BatchPlanner::image_geometry(Item &it, ImgDesc &im) {
         if (b->lossless) im.out[c] = im.in[c];
         else fill_geom(o.comp[c], im.out[c], b->ntiles_out);  // rebased behind all decoded tiles below
         im.comp_id[c] = o.comp[c].id;
-        std::vector<uint16_t> key(in.qt[in.comp[c].tq], in.qt[in.comp[c].tq] + 64);
+        std::vector<uint16_t> key(in.comp[c].qt, in.comp[c].qt + 64);
         auto f = quant_index.find(key);
         if (f == quant_index.end()) {
             DevQuant q; make_quant(key.data(), q);
@@ -599,7 +603,7 @@ int BatchPlanner::decode_scans(Item &it, ImgDesc &im, const uint8_t *d) {
         if (js.ncomp > CSH_MAX_COMPS) { it.code = CS_ERR_JPEG_FEATURE; it.msg = "scan with more than 3 components"; break; }
         for (int k = 0; k < js.ncomp; k++) { ds.comp[k] = js.comp_idx[k]; ds.td[k] = js.td[k]; ds.ta[k] = js.ta[k]; }
         ds.Ss = js.Ss; ds.Se = js.Se; ds.Ah = js.Ah; ds.Al = js.Al;
-        ds.restart_interval = in.restart_interval;
+        ds.restart_interval = js.restart_interval;
         ds.par_index = -1;
         ds.huff_set = huff_set(js);
         // tables the scan needs must exist
@@ -665,13 +669,13 @@ int BatchPlanner::sequential_split(const Item &it, const ImgDesc &im, const uint
     for (size_t s = 0; s < in.scans.size() && par_ok; s++) {
         const JScan &js = in.scans[s];
         const uint32_t units = scan_units(in, js);
-        if (in.restart_interval == 0) {
+        if (js.restart_interval == 0) {
             if (js.has_marker) par_ok = false;   // marker bytes inside the data: leave it to the sequential kernel's libjpeg-like handling
             else pieces[s].push_back({js.data_off, js.data_len, 0u, units});
             continue;
         }
         // restart intervals: RSTm markers must come in order, one after every `restart_interval` MCUs, none missing
-        const uint32_t ri = uint32_t(in.restart_interval), want = (units + ri - 1) / ri;
+        const uint32_t ri = uint32_t(js.restart_interval), want = (units + ri - 1) / ri;
         size_t pos = js.data_off, end = js.data_off + js.data_len, start = pos;
         uint32_t idx = 0;
         bool ok = true;
@@ -691,13 +695,17 @@ int BatchPlanner::sequential_split(const Item &it, const ImgDesc &im, const uint
         if (ok) pieces[s].push_back({start, end - start, idx * ri, std::min(ri, units - idx * ri)});
         if (!ok || pieces[s].size() != want) par_ok = false;
     }
+    // the unstuffing pass finds a byte's ParScan by bisection: the list stays sorted by bits_off.  A file with a restart interval in any scan
+    // therefore gets every piece copied behind what the pool holds, a scan without restarts among them
+    bool any_restart = false;
+    for (const JScan &js : in.scans) any_restart = any_restart || js.restart_interval != 0;
     for (size_t s = 0; s < in.scans.size() && par_ok; s++) {   // one ParScan per piece
         const JScan &js = in.scans[s];
         const DecScan &ds = b->dec.dscans[im.first_scan + s];
         for (const Piece &pc : pieces[s]) {
             ParScan ps;
             memset(&ps, 0, sizeof ps);
-            if (in.restart_interval == 0) { ps.bits_off = ds.bits_off; ps.bits_len = ds.bits_len; }
+            if (!any_restart) { ps.bits_off = ds.bits_off; ps.bits_len = ds.bits_len; }
             else {
                 ps.bits_off = uint32_t(b->dec.bits_pool.size()); ps.bits_len = uint32_t(pc.len);
                 if (!b->dec.bits_pool.append_aligned(d + pc.off, pc.len)) { csh_set_error("out of pinned host memory"); return CS_ERR_NO_DEVICE; }
@@ -735,10 +743,10 @@ static bool regular_progression(const JpegInfo &in) {
 // of kind 1 so that the unstuffing pre-pass covers them
 bool BatchPlanner::progressive_plan(const Item &it, const ImgDesc &im, int img_index) {
     const JpegInfo &in = it.in;
-    bool prog_ok = in.progressive && in.restart_interval == 0;
+    bool prog_ok = in.progressive;
     for (size_t s = 0; s < in.scans.size(); s++) {
         const JScan &js = in.scans[s];
-        if (js.has_marker || js.data_len >= (1u << 28) || !b->dec.phset_fits[b->dec.dscans[im.first_scan + s].huff_set]) prog_ok = false;
+        if (js.restart_interval != 0 || js.has_marker || js.data_len >= (1u << 28) || !b->dec.phset_fits[b->dec.dscans[im.first_scan + s].huff_set]) prog_ok = false;
     }
     if (!prog_ok) return false;
     // The scans of a progressive file, by what they are to the decoder (k_decode_par.hip, k_decode_prog.hip):

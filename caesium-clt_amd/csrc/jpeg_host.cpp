@@ -44,6 +44,7 @@ int parse_jpeg(const uint8_t *d, size_t n, JpegInfo &j, std::string &msg) {
     if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) BAD(CS_ERR_BAD_JPEG, "not a JPEG stream (missing SOI)");
     HuffSpec dc[4], ac[4];
     bool have_sof = false;
+    int dri = 0;   // DRI, DHT and DQT are state that the scans after them see: each SOS records (or latches) what is in force
     size_t i = 2;
     while (i + 4 <= n) {
         if (d[i] != 0xFF) { i++; continue; }
@@ -120,7 +121,7 @@ int parse_jpeg(const uint8_t *d, size_t n, JpegInfo &j, std::string &msg) {
             break;
         }
         case 0xDD:
-            if (sl >= 2) j.restart_interval = (s[0] << 8) | s[1];
+            if (sl >= 2) dri = (s[0] << 8) | s[1];
             break;
         case 0xDA: {
             if (!have_sof) BAD(CS_ERR_BAD_JPEG, "SOS before SOF");
@@ -137,7 +138,10 @@ int parse_jpeg(const uint8_t *d, size_t n, JpegInfo &j, std::string &msg) {
                 sc.comp_idx[k] = ci;
                 sc.td[k] = s[2 + 2 * k] >> 4;
                 sc.ta[k] = s[2 + 2 * k] & 15;
+                JComp &jc = j.comp[ci];
+                if (!jc.qt_latched && j.qt_present[jc.tq]) { memcpy(jc.qt, j.qt[jc.tq], sizeof jc.qt); jc.qt_latched = true; }
             }
+            sc.restart_interval = dri;
             sc.Ss = s[1 + 2 * ns]; sc.Se = s[2 + 2 * ns];
             sc.Ah = s[3 + 2 * ns] >> 4; sc.Al = s[3 + 2 * ns] & 15;
             if (!j.progressive) { sc.Ss = 0; sc.Se = 63; sc.Ah = sc.Al = 0; }
@@ -181,6 +185,8 @@ int parse_jpeg(const uint8_t *d, size_t n, JpegInfo &j, std::string &msg) {
     if (j.scans.empty()) BAD(CS_ERR_BAD_JPEG, "no scan data");
     for (int c = 0; c < j.ncomp; c++)
         if (!j.qt_present[j.comp[c].tq]) BAD(CS_ERR_BAD_JPEG, "missing quantisation table");
+    for (int c = 0; c < j.ncomp; c++)   // no scan found the slot filled: the file's last word on it
+        if (!j.comp[c].qt_latched) memcpy(j.comp[c].qt, j.qt[j.comp[c].tq], sizeof j.comp[c].qt);
     return 0;
 }
 

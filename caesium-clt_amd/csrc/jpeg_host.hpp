@@ -26,20 +26,24 @@ struct JScan {
     size_t data_off = 0, data_len = 0;  // entropy-coded segment inside the file
     bool has_marker = false;            // an 0xFF followed by anything but 0x00 lies inside the segment (RSTn, or garbage)
     HuffSpec dc[4], ac[4];              // tables in force at SOS
+    int restart_interval = 0;           // DRI in force at SOS: MCUs, or blocks of a one-component scan (0: no restart markers)
 };
 
 struct JComp {
     int id = 0, h = 1, v = 1, tq = 0;
     int comp_w = 0, comp_h = 0, real_bw = 0, real_bh = 0, bw = 0, bh = 0;
+    // the table the component is decoded with: slot tq as it is when the component's first scan starts (libjpeg latch_quant_tables);
+    // a later DQT that redefines the slot does not reach it.  Natural order
+    uint16_t qt[64] = {0};
+    bool qt_latched = false;
 };
 
 struct JpegInfo {
     int width = 0, height = 0, ncomp = 0;
     bool progressive = false;
     int hmax = 1, vmax = 1, mcus_x = 0, mcus_y = 0;
-    int restart_interval = 0;
     JComp comp[4];
-    uint16_t qt[4][64] = {{0}};  // natural order
+    uint16_t qt[4][64] = {{0}};  // the slots as the file leaves them, natural order (decoding uses JComp::qt)
     bool qt_present[4] = {false, false, false, false};
     std::vector<JScan> scans;
     std::vector<uint8_t> meta;  // APPn / COM segments, raw, file order

@@ -25,9 +25,11 @@ __device__ static inline void br_fill(BitReader &b) {
         if (!b.marker && b.p < b.end) {
             c = *b.p;
             if (c == 0xFF) {
-                int c2 = (b.p + 1 < b.end) ? b.p[1] : 0xD9;
-                if (c2 == 0) b.p += 2;
-                else { b.marker = c2; c = 0; }
+                const uint8_t *q = b.p + 1;
+                while (q < b.end && *q == 0xFF) q++;   // fill bytes in front of a marker (T.81 B.1.1.2), skipped as libjpeg skips them
+                int c2 = (q < b.end) ? *q : 0xD9;
+                if (c2 == 0) b.p = q + 1;
+                else { b.marker = c2; b.p = q - 1; c = 0; }   // p: the 0xFF next to the marker code (restart() steps over both)
             } else b.p++;
             if (!b.marker) b.real += 8;
         }

@@ -140,9 +140,12 @@ static void br_fill(breader *b) {
         if (!b->hit_marker && b->p < b->end) {
             c = *b->p;
             if (c == 0xFF) {
-                if (b->p + 1 < b->end && b->p[1] == 0x00) b->p += 2;
-                else { /* marker (or truncated): feed zeros from here on */
-                    b->hit_marker = (b->p + 1 < b->end) ? b->p[1] : 0xD9;
+                const uint8_t *q = b->p + 1;
+                while (q < b->end && *q == 0xFF) q++;   /* fill bytes in front of a marker (T.81 B.1.1.2; libjpeg jdhuff.c skips them too) */
+                if (q < b->end && *q == 0x00) b->p = q + 1;
+                else { /* marker (or truncated): feed zeros from here on; p is left on the 0xFF next to the marker code */
+                    b->hit_marker = (q < b->end) ? *q : 0xD9;
+                    b->p = q - 1;
                     c = 0;
                 }
             } else b->p++;
@@ -392,6 +395,10 @@ int cso_decode(const uint8_t *d, size_t n, cso_image **out) {
                 if (ci < 0) { snprintf(g_err, sizeof g_err, "SOS names unknown component"); goto done; }
                 for (int q = 0; q < k; q++) if (sc->comp_idx[q] == ci) { snprintf(g_err, sizeof g_err, "SOS names a component twice"); goto done; }  /* libjpeg JERR_BAD_COMPONENT_ID */
                 sc->comp_idx[k] = ci; td[k] = s[2 + 2 * k] >> 4; ta[k] = s[2 + 2 * k] & 15;   /* a number >= 4 fails when the table is needed (libjpeg: JERR_NO_HUFF_TABLE) */
+                /* libjpeg jdinput.c latch_quant_tables: a component keeps the contents its slot has when its first scan starts */
+                if (!im->comp_qt_latched[ci] && im->comp[ci].tq >= 0 && im->comp[ci].tq <= 3 && im->qt_present[im->comp[ci].tq]) {
+                    memcpy(im->comp_qt[ci], im->qt[im->comp[ci].tq], sizeof im->comp_qt[ci]); im->comp_qt_latched[ci] = 1;
+                }
             }
             sc->Ss = s[1 + 2 * ns]; sc->Se = s[2 + 2 * ns]; sc->Ah = s[3 + 2 * ns] >> 4; sc->Al = s[3 + 2 * ns] & 15;
             if (!im->progressive) { sc->Ss = 0; sc->Se = 63; sc->Ah = sc->Al = 0; }
@@ -567,11 +574,12 @@ void cso_dering_block(int32_t data[64], int dc_quant) {
 /* decode to samples                                                                          */
 int cso_decode_plane(const cso_image *im, int ci, uint8_t *out) {
     const cso_comp *k = &im->comp[ci];
-    if (!im->qt_present[k->tq]) FAIL("missing quantisation table %d", k->tq);
+    if (!im->comp_qt_latched[ci] && !im->qt_present[k->tq]) FAIL("missing quantisation table %d", k->tq);
+    const uint16_t *qt = im->comp_qt_latched[ci] ? im->comp_qt[ci] : im->qt[k->tq];   /* not latched: an image made by cso_forward */
     uint8_t px[64];
     for (int by = 0; by < k->real_bh; by++)
         for (int bx = 0; bx < k->real_bw; bx++) {
-            cso_idct_islow(k->coef + ((size_t)by * k->bw + bx) * 64, im->qt[k->tq], px);
+            cso_idct_islow(k->coef + ((size_t)by * k->bw + bx) * 64, qt, px);
             for (int y = 0; y < 8; y++) {
                 int yy = by * 8 + y; if (yy >= k->comp_h) break;
                 for (int x = 0; x < 8; x++) { int xx = bx * 8 + x; if (xx < k->comp_w) out[(size_t)yy * k->comp_w + xx] = px[8 * y + x]; }
@@ -1393,7 +1401,15 @@ int cso_jpeg_compress(const uint8_t *in, size_t n, const cso_enc_params *p, int 
     cso_image *src = NULL, *dst = NULL;
     if (cso_decode(in, n, &src)) return -1;
     int rc = -1;
-    if (lossless) { rc = cso_encode(src, p, NULL, 0, out, out_len); cso_image_free(src); return rc; }
+    if (lossless) {
+        /* libjpeg jctrans.c jpeg_copy_critical_parameters: the output takes the slots as the file left them, and a component that latched
+           other contents cannot be carried over (JERR_MISMATCHED_QUANT_TABLE) */
+        for (int c = 0; c < src->ncomp; c++)
+            if (src->comp_qt_latched[c] && memcmp(src->comp_qt[c], src->qt[src->comp[c].tq], sizeof src->comp_qt[c])) {
+                cso_image_free(src); FAIL("unsupported: component %d was decoded with a quantisation table that its slot no longer holds", c);
+            }
+        rc = cso_encode(src, p, NULL, 0, out, out_len); cso_image_free(src); return rc;
+    }
     if (decode_resize_forward(src, p, 0, 0, 0, &dst, NULL) == 0) {
         dst->meta = src->meta; dst->meta_len = src->meta_len;
         rc = cso_encode(dst, p, NULL, 0, out, out_len);

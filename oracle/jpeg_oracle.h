@@ -56,6 +56,9 @@ typedef struct {
        (FF Mx len.. payload) of APPn/COM in file order */
     uint8_t *meta; size_t meta_len;
     int saw_jfif, adobe_transform;
+    /* decoded images: the table each component dequantises with, copied from its slot when its first scan starts (natural order) */
+    uint16_t comp_qt[CSO_MAX_COMPS][64];
+    int comp_qt_latched[CSO_MAX_COMPS];
 } cso_image;
 
 typedef struct {

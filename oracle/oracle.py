@@ -36,7 +36,7 @@ class Image(C.Structure):
                 ("progressive", C.c_int), ("hmax", C.c_int), ("vmax", C.c_int), ("mcus_x", C.c_int), ("mcus_y", C.c_int),
                 ("restart_interval", C.c_int), ("comp", Comp * 4), ("qt", (C.c_uint16 * 64) * 4), ("qt_present", C.c_int * 4),
                 ("nscans", C.c_int), ("scans", Scan * 64), ("meta", C.POINTER(C.c_uint8)), ("meta_len", C.c_size_t),
-                ("saw_jfif", C.c_int), ("adobe_transform", C.c_int)]
+                ("saw_jfif", C.c_int), ("adobe_transform", C.c_int), ("comp_qt", (C.c_uint16 * 64) * 4), ("comp_qt_latched", C.c_int * 4)]
 
 
 class EncParams(C.Structure):

@@ -4,7 +4,8 @@ Pillow/libjpeg-turbo writes 4:4:4, 4:2:2 and 4:2:0 only; the layout tests need 4
 sampled differently.  This writer makes them from the seeded synthetic pictures of tools/gen_synth.py: JFIF YCbCr, each component point-sampled
 to its own size (what the pixels are does not matter to a decoder test, only that they vary), an orthonormal float DCT, the Annex K quantisation
 tables at a quality, and one fixed-length Huffman code per table class (every DC category 4 bits, every AC symbol 8 bits -- a valid DHT
-that needs no statistics).  One interleaved sequential scan, with an optional restart interval.  Progressive variants come from the oracle's
+that needs no statistics).  One interleaved sequential scan, with an optional restart interval -- or a list of scans (all components
+interleaved, or one component each), every one with DRI segments of its own in front.  Progressive variants come from the oracle's
 lossless transcode (oracle_lossless(src, progressive=1)), which keeps the layout.
 """
 import numpy as np
@@ -72,8 +73,11 @@ def _bits_of(v, size):
     return int(v) if v >= 0 else int(v) + (1 << size) - 1
 
 
-def write_jpeg(rgb, layout, quality=85, restart_interval=0):
-    """(h, w, 3) uint8 RGB -> baseline JPEG bytes with the given ((h, v) x 3) sampling factors"""
+def write_jpeg(rgb, layout, quality=85, restart_interval=0, scans=None):
+    """(h, w, 3) uint8 RGB -> baseline JPEG bytes with the given ((h, v) x 3) sampling factors.
+    scans: [(components, dri)] in file order; components (0, 1, 2) for an interleaved scan or (c,) for a scan of one component, whose
+    restart interval counts the blocks of ceil(comp_w / 8) x ceil(comp_h / 8); dri None (no DRI segment: the interval in force stays),
+    a value, or a tuple of values written as one DRI segment each in front of the SOS (0 switches restarts off)"""
     rgb = np.asarray(rgb, dtype=np.float64)
     H, W = rgb.shape[:2]
     r, g, b = rgb[..., 0], rgb[..., 1], rgb[..., 2]
@@ -94,7 +98,7 @@ def write_jpeg(rgb, layout, quality=85, restart_interval=0):
         q = np.round(coef / qt[min(c, 1)]).astype(np.int64)[:, :, _ZZ]
         q[:, :, 0] = np.clip(q[:, :, 0], -1023, 1023)
         q[:, :, 1:] = np.clip(q[:, :, 1:], -1023, 1023)
-        comps.append((h, v, q))
+        comps.append((h, v, q, -(-cw // 8), -(-ch // 8)))
 
     def seg(marker, payload):
         return bytes([0xFF, marker]) + (len(payload) + 2).to_bytes(2, "big") + payload
@@ -110,46 +114,60 @@ def write_jpeg(rgb, layout, quality=85, restart_interval=0):
     for t in range(2):   # DC class: categories 0..11, 4 bits each; AC class: 162 symbols, 8 bits each
         out += seg(0xC4, bytes([t]) + bytes([0, 0, 0, 12] + [0] * 12) + bytes(range(12)))
         out += seg(0xC4, bytes([0x10 | t]) + bytes([0] * 7 + [len(_AC_SYMS)] + [0] * 8) + bytes(_AC_SYMS))
-    if restart_interval:
-        out += seg(0xDD, restart_interval.to_bytes(2, "big"))
-    out += seg(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
     ac_code = {s: i for i, s in enumerate(_AC_SYMS)}
-    bits = _Bits()
-    pred = [0, 0, 0]
-    nmcu, rst = mx * my, 0
-    for m in range(nmcu):
-        if restart_interval and m and m % restart_interval == 0:
-            bits.flush()
-            bits.out += bytes([0xFF, 0xD0 + rst])
-            rst = (rst + 1) & 7
-            pred = [0, 0, 0]
-        mby, mbx = divmod(m, mx)
-        for c, (h, v, q) in enumerate(comps):
-            for yy in range(v):
-                for xx in range(h):
-                    blk = q[mby * v + yy, mbx * h + xx]
-                    d = int(blk[0]) - pred[c]
-                    pred[c] = int(blk[0])
-                    s = _category(d)
-                    bits.put(s, 4)
-                    if s:
-                        bits.put(_bits_of(d, s), s)
-                    run = 0
-                    nz = np.flatnonzero(blk[1:]) + 1
-                    last = 0
-                    for k in nz:
-                        run = k - last - 1
-                        while run > 15:
-                            bits.put(ac_code[0xF0], 8)
-                            run -= 16
-                        s = _category(blk[k])
-                        bits.put(ac_code[(run << 4) | s], 8)
-                        bits.put(_bits_of(blk[k], s), s)
-                        last = k
-                    if last != 63:
-                        bits.put(ac_code[0x00], 8)
-    bits.flush()
-    out += bits.out + b"\xff\xd9"
+    if scans is None:
+        scans = [((0, 1, 2), restart_interval or None)]
+    for group, dri in scans:
+        assert len(group) == 1 or tuple(group) == (0, 1, 2), "an interleaved scan takes every component"
+        for value in (() if dri is None else dri if isinstance(dri, tuple) else (dri,)):
+            out += seg(0xDD, value.to_bytes(2, "big"))
+            restart_interval = value
+        out += seg(0xDA, bytes([len(group)]) + b"".join(bytes([c + 1, 0x11 if c else 0x00]) for c in group) + bytes([0, 63, 0]))
+        bits = _Bits()
+        pred = [0, 0, 0]
+
+        def code_block(c, blk):
+            d = int(blk[0]) - pred[c]
+            pred[c] = int(blk[0])
+            s = _category(d)
+            bits.put(s, 4)
+            if s:
+                bits.put(_bits_of(d, s), s)
+            run = 0
+            nz = np.flatnonzero(blk[1:]) + 1
+            last = 0
+            for k in nz:
+                run = k - last - 1
+                while run > 15:
+                    bits.put(ac_code[0xF0], 8)
+                    run -= 16
+                s = _category(blk[k])
+                bits.put(ac_code[(run << 4) | s], 8)
+                bits.put(_bits_of(blk[k], s), s)
+                last = k
+            if last != 63:
+                bits.put(ac_code[0x00], 8)
+
+        one = len(group) == 1
+        across = comps[group[0]][3] if one else mx
+        nunit, rst = across * (comps[group[0]][4] if one else my), 0
+        for m in range(nunit):
+            if restart_interval and m and m % restart_interval == 0:
+                bits.flush()
+                bits.out += bytes([0xFF, 0xD0 + rst])
+                rst = (rst + 1) & 7
+                pred = [0, 0, 0]
+            mby, mbx = divmod(m, across)
+            if one:
+                code_block(group[0], comps[group[0]][2][mby, mbx])
+                continue
+            for c, (h, v, q, _, _) in enumerate(comps):
+                for yy in range(v):
+                    for xx in range(h):
+                        code_block(c, q[mby * v + yy, mbx * h + xx])
+        bits.flush()
+        out += bits.out
+    out += b"\xff\xd9"
     return bytes(out)
 
 
