@@ -3,7 +3,8 @@ repository's inflate kernel: it decodes a stream and keeps, for every dynamic bl
 each of their symbols is actually used -- the code-length symbols of the block's own header included.  tests/test_code_tables_emul.py holds those
 lengths to tests/_prefix_model.py.
 
-    blocks, data = read(raw_deflate)      blocks: [Block]; a Block of type 2 has cl_len / cl_count (19), ll_len / ll_count (286), d_len / d_count (30)
+    blocks, data = read(raw_deflate)      blocks: [Block]; a Block of type 2 has cl_len / cl_count (19), ll_len / ll_count (286), d_len / d_count (30);
+                                          one of type 1 or 2 has tokens
     blocks, data = read_png(png_bytes)    the concatenated IDAT chunks without the zlib wrapper
 """
 import zlib
@@ -46,7 +47,8 @@ class Code:
 
 
 class Block:
-    """btype 0 stored, 1 fixed, 2 dynamic; final; for a dynamic block the lengths as transmitted (padded with zeros to the whole alphabet) and the counts"""
+    """btype 0 stored, 1 fixed, 2 dynamic; final; for a dynamic block the lengths as transmitted (padded with zeros to the whole alphabet) and the counts;
+    for every block that is not stored its tokens in stream order, (0, byte) or (length, distance)"""
 
 
 def _fixed():
@@ -87,11 +89,13 @@ def read(raw):
                 b.ll_len, b.d_len = lens[:hlit] + [0] * (286 - hlit), lens[hlit:] + [0] * (30 - hdist)
                 assert b.ll_len[256], "no end-of-block code"
                 ll, dd = Code(b.ll_len), Code(b.d_len) if any(b.d_len) else None
-            b.ll_count, b.d_count = [0] * 286, [0] * 30
+            b.ll_count, b.d_count, b.tokens = [0] * 286, [0] * 30, []
             while True:
                 s = ll.read(br)
                 b.ll_count[s] += 1
-                if s < 256: out.append(s)
+                if s < 256:
+                    out.append(s)
+                    b.tokens.append((0, s))
                 elif s == 256: break
                 else:
                     n = LEN_BASE[s - 257] + br.read(LEN_EXTRA[s - 257])
@@ -100,6 +104,7 @@ def read(raw):
                     dist = DIST_BASE[d] + br.read(DIST_EXTRA[d])
                     assert dist <= len(out), "a distance in front of the stream"
                     for _ in range(n): out.append(out[-dist])
+                    b.tokens.append((n, dist))
         assert br.pos <= br.nbits, "the stream ends inside a block"
         if b.final:
             return blocks, bytes(out)
