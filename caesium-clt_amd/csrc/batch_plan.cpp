@@ -9,6 +9,7 @@
 
 #include "batch.hpp"
 #include "resize_host.h"
+#include "result.h"
 
 namespace csh {
 
@@ -132,16 +133,6 @@ static void add_script(std::vector<EncScan> &v, int ncomp, bool progressive) {
         }
         v.push_back(e);
     }
-}
-
-static bool is_jpeg(const uint8_t *d, size_t n) { return n >= 3 && d[0] == 0xFF && d[1] == 0xD8 && d[2] == 0xFF; }
-static int sniff_type(const uint8_t *d, size_t n) {
-    if (is_jpeg(d, n)) return CS_TYPE_JPEG;
-    if (n >= 8 && !memcmp(d, "\x89PNG\r\n\x1a\n", 8)) return CS_TYPE_PNG;
-    if (n >= 12 && !memcmp(d, "RIFF", 4) && !memcmp(d + 8, "WEBP", 4)) return CS_TYPE_WEBP;
-    if (n >= 6 && (!memcmp(d, "GIF87a", 6) || !memcmp(d, "GIF89a", 6))) return CS_TYPE_GIF;
-    if (n >= 4 && (!memcmp(d, "II*\0", 4) || !memcmp(d, "MM\0*", 4))) return CS_TYPE_TIFF;
-    return CS_TYPE_UNKN;
 }
 
 // decoded plane -> full resolution: libjpeg-turbo's choice of upsampling method (jdsample.c jinit_upsampler), cw the downsampled width
@@ -489,7 +480,7 @@ void BatchPlanner::parse() {
         for (size_t n; (n = next++) < count;) {
             Item &it = b->items[n];
             it.file_size = inputs[n].length;
-            int type = sniff_type(inputs[n].data, inputs[n].length);
+            int type = sniff(inputs[n].data, inputs[n].length);
             if (type == CS_TYPE_UNKN) { it.code = CS_ERR_UNKNOWN_TYPE; it.msg = "unknown file type"; }
             else if (type != CS_TYPE_JPEG) { it.code = CS_ERR_UNSUPPORTED; it.msg = "this input format has no device path in this build (built: JPEG, PNG)"; }
             else it.code = parse_jpeg(inputs[n].data, inputs[n].length, it.in, it.msg);

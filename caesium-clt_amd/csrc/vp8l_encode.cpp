@@ -4,22 +4,17 @@
 #include <cstring>
 #include <vector>
 
-#include "../../include/caesium_hip.h"
 #include "devmem.hpp"
+#include "riff.h"
+#include "routes.hpp"
 #include "webp_kernels.h"
 
 using namespace csh;
 
-static CCSResult make_res(uint32_t code, const char *msg) {
-    CCSResult r; r.success = code == 0; r.code = code; r.error_message = nullptr;
-    if (code && msg) { size_t n = strlen(msg); char *m = static_cast<char *>(malloc(n + 1)); memcpy(m, msg, n + 1); r.error_message = m; }
-    return r;
-}
-
 extern "C" int csl_encode_pixels(const csp_pixels *px, size_t count, int device, CByteArray *outputs, CCSResult *results) {
     for (size_t i = 0; i < count; i++) { outputs[i].data = nullptr; outputs[i].length = 0; }
     if (csh_device_count() <= device || hipSetDevice(device) != hipSuccess) {
-        for (size_t i = 0; i < count; i++) results[i] = make_res(CS_ERR_NO_DEVICE, "no HIP device available (libcaesium_hip has no CPU path)");
+        for (size_t i = 0; i < count; i++) results[i] = make_result(CS_ERR_NO_DEVICE, "no HIP device available (libcaesium_hip has no CPU path)");
         return int(count);
     }
     // the coder, read on every call: unset / empty / "plain" = literals only (the bytes oracle/png_oracle.c cso_vp8l_encode states), "refs" = backward
@@ -33,7 +28,7 @@ extern "C" int csl_encode_pixels(const csp_pixels *px, size_t count, int device,
     const bool palette = groups || (mode && !strcmp(mode, "palette"));
     const bool refs = palette || (mode && !strcmp(mode, "refs"));
     if (mode && *mode && !refs && strcmp(mode, "plain")) {
-        for (size_t i = 0; i < count; i++) results[i] = make_res(CS_ERR_UNSUPPORTED, "CSH_VP8L names no lossless WebP coder (plain, refs, palette, groups, far)");
+        for (size_t i = 0; i < count; i++) results[i] = make_result(CS_ERR_UNSUPPORTED, "CSH_VP8L names no lossless WebP coder (plain, refs, palette, groups, far)");
         return int(count);
     }
     int failed = 0;
@@ -44,7 +39,7 @@ extern "C" int csl_encode_pixels(const csp_pixels *px, size_t count, int device,
     for (size_t i = 0; i < count; i++) {
         const uint32_t ch = px[i].channels;
         if (!((ch >= 1 && ch <= 4) || ch == csw::VP8L_ALPHA_OF + 2 || ch == csw::VP8L_ALPHA_OF + 4) || !px[i].width || !px[i].height || px[i].width > 16384 || px[i].height > 16384) {
-            results[i] = make_res(CS_ERR_UNSUPPORTED, "lossless WebP output takes 8-bit grey / RGB pictures, with or without alpha, of at most 16384 x 16384"); failed++; continue;
+            results[i] = make_result(CS_ERR_UNSUPPORTED, "lossless WebP output takes 8-bit grey / RGB pictures, with or without alpha, of at most 16384 x 16384"); failed++; continue;
         }
         csw::Vp8lImg im;
         memset(&im, 0, sizeof im);
@@ -54,7 +49,7 @@ extern "C" int csl_encode_pixels(const csp_pixels *px, size_t count, int device,
         im.res_off = work; work += (npx + 63) & ~uint64_t(63);
         im.mode_off = modes; modes += (uint64_t(im.bw) * im.bh + 63) & ~uint64_t(63);
         const uint64_t cap = 8 * npx + 2 * uint64_t(im.bw) * im.bh + 8192;   // four codes of at most 15 bits per pixel, the mode image, the code descriptions
-        if (cap > 0xFFFFFFF0ull) { results[i] = make_res(CS_ERR_UNSUPPORTED, "picture too large for one lossless WebP batch item"); failed++; continue; }
+        if (cap > 0xFFFFFFF0ull) { results[i] = make_result(CS_ERR_UNSUPPORTED, "picture too large for one lossless WebP batch item"); failed++; continue; }
         im.out_off = out; im.out_cap = uint32_t(cap); out += (cap + 255) & ~uint64_t(255);   // (the refs stream is written only where it is the smaller one)
         if (refs) {
             im.nchunk = uint32_t((npx + csw::VP8L_CHUNK - 1) / csw::VP8L_CHUNK);
@@ -164,14 +159,14 @@ extern "C" int csl_encode_pixels(const csp_pixels *px, size_t count, int device,
     }
     for (size_t k = 0; k < nparent; k++) {
         const size_t i = at[k];
-        if (!ok) { results[i] = make_res(CS_ERR_NO_DEVICE, "lossless WebP coding failed on the device"); failed++; continue; }
-        if (status[k] || !len[k]) { results[i] = make_res(CS_ERR_POOL_OVERFLOW, "lossless WebP output larger than its region"); failed++; continue; }
+        if (!ok) { results[i] = make_result(CS_ERR_NO_DEVICE, "lossless WebP coding failed on the device"); failed++; continue; }
+        if (status[k] || !len[k]) { results[i] = make_result(CS_ERR_POOL_OVERFLOW, "lossless WebP output larger than its region"); failed++; continue; }
         outputs[i].data = static_cast<uint8_t *>(malloc(len[k]));
         if (!outputs[i].data || csh_copy_wait(outputs[i].data, d_out.p + imgs[k].out_off, len[k], hipMemcpyDeviceToHost, st) != hipSuccess) {
-            free(outputs[i].data); outputs[i].data = nullptr; results[i] = make_res(CS_ERR_NO_DEVICE, "D2H failed"); failed++; continue;
+            free(outputs[i].data); outputs[i].data = nullptr; results[i] = make_result(CS_ERR_NO_DEVICE, "D2H failed"); failed++; continue;
         }
         outputs[i].length = len[k];
-        results[i] = make_res(0, nullptr);
+        results[i] = make_result(0, nullptr);
     }
     if (have_st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }   // nothing queued may outlive the device blocks
     return failed;
@@ -183,21 +178,32 @@ extern "C" int csl_encode_pixels(const csp_pixels *px, size_t count, int device,
 extern "C" int csl_attach_alpha(CByteArray *lossy, const CByteArray *alpha_vp8l, uint32_t width, uint32_t height) {
     if (!lossy || !lossy->data || lossy->length < 30 || memcmp(lossy->data + 12, "VP8 ", 4) || !alpha_vp8l || !alpha_vp8l->data || alpha_vp8l->length < 26 || memcmp(alpha_vp8l->data + 12, "VP8L", 4)) return -1;
     const uint8_t *a = alpha_vp8l->data;
-    const size_t pl = size_t(a[16]) | (size_t(a[17]) << 8) | (size_t(a[18]) << 16) | (size_t(a[19]) << 24);
+    const size_t pl = riff::rd32(a + 16);
     if (pl < 5 || 20 + pl > alpha_vp8l->length) return -1;
     const size_t vp8 = lossy->length - 12, apay = pl - 5, alph = 1 + apay, total = 12 + 18 + 8 + alph + (alph & 1) + vp8;
-    uint8_t *o = static_cast<uint8_t *>(malloc(total)), *w = o;
+    uint8_t *o = static_cast<uint8_t *>(malloc(total));
     if (!o) return -1;
-    auto le32 = [](uint8_t *q, uint32_t v) { q[0] = uint8_t(v); q[1] = uint8_t(v >> 8); q[2] = uint8_t(v >> 16); q[3] = uint8_t(v >> 24); };
-    memcpy(w, "RIFF", 4); le32(w + 4, uint32_t(total - 8)); memcpy(w + 8, "WEBPVP8X", 8); le32(w + 16, 10);
-    w[20] = 0x10; w[21] = w[22] = w[23] = 0;
-    const uint32_t cw = width - 1, ch = height - 1;
-    w[24] = uint8_t(cw); w[25] = uint8_t(cw >> 8); w[26] = uint8_t(cw >> 16); w[27] = uint8_t(ch); w[28] = uint8_t(ch >> 8); w[29] = uint8_t(ch >> 16);
-    w += 30;
-    memcpy(w, "ALPH", 4); le32(w + 4, uint32_t(alph)); w[8] = 0x01; memcpy(w + 9, a + 25, apay); w += 8 + alph;
+    uint8_t *w = riff::write_vp8x(riff::write_header(o, total), 0x10, width, height);
+    memcpy(w, "ALPH", 4); riff::wr32(w + 4, uint32_t(alph)); w[8] = 0x01; memcpy(w + 9, a + 25, apay); w += 8 + alph;   // (no append_chunk: the payload is put together in place)
     if (alph & 1) *w++ = 0;
     memcpy(w, lossy->data + 12, vp8);
     free(lossy->data);
     lossy->data = o; lossy->length = total;
     return 0;
+}
+
+int route::attach_alpha_planes(const std::vector<csp_pixels> &planes, const std::vector<size_t> &whose, CByteArray *outs, CCSResult *results, int device) {
+    std::vector<CByteArray> aout(planes.size());
+    std::vector<CCSResult> ares(planes.size());
+    csl_encode_pixels(planes.data(), planes.size(), device, aout.data(), ares.data());
+    int failed = 0;
+    for (size_t j = 0; j < planes.size(); j++) {
+        const size_t k = whose[j];
+        if (!aout[j].data || csl_attach_alpha(&outs[k], &aout[j], planes[j].width, planes[j].height)) {
+            cs_free_bytes(&outs[k]); cs_free_result(&results[k]);
+            results[k] = make_result(ares[j].code ? ares[j].code : CS_ERR_NO_DEVICE, "alpha plane coder failed"); failed++;
+        }
+        cs_free_bytes(&aout[j]); cs_free_result(&ares[j]);
+    }
+    return failed;
 }

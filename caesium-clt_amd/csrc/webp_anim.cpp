@@ -8,19 +8,12 @@
 #include <algorithm>
 #include <cstring>
 
+#include "riff.h"
+#include "routes.hpp"
 #include "webp_anim.hpp"
 
 using namespace csh;
-
-static uint32_t rd24(const uint8_t *d) { return uint32_t(d[0]) | (uint32_t(d[1]) << 8) | (uint32_t(d[2]) << 16); }
-static uint32_t rd32(const uint8_t *d) { return rd24(d) | (uint32_t(d[3]) << 24); }
-static void wr24(uint8_t *q, uint32_t v) { q[0] = uint8_t(v); q[1] = uint8_t(v >> 8); q[2] = uint8_t(v >> 16); }
-static void wr32(uint8_t *q, uint32_t v) { wr24(q, v); q[3] = uint8_t(v >> 24); }
-static CCSResult make_res(uint32_t code, const char *msg) {
-    CCSResult r; r.success = code == 0; r.code = code; r.error_message = nullptr;
-    if (code && msg) { size_t n = strlen(msg); char *m = static_cast<char *>(malloc(n + 1)); memcpy(m, msg, n + 1); r.error_message = m; }
-    return r;
-}
+using riff::rd24; using riff::rd32; using riff::wr24; using riff::wr32;
 
 // AnimDecoder's key frames: the first; a frame that covers the canvas and does not blend; a frame behind one that disposed to the background and either covered
 // the canvas or was a key frame itself (nothing of an older canvas is left then)
@@ -36,16 +29,14 @@ static void anim_key_frames(cswd_anim &a) {
 }
 
 int cswd_parse_anim(const uint8_t *d, size_t n, cswd_anim &a, std::vector<cswd_frame_src> &src, std::string &msg) {
-    size_t end = size_t(rd32(d + 4)) + 8;
-    if (end > n) end = n;
     bool have_canvas = false, have_anim = false;
-    for (size_t i = 12; i + 8 <= end;) {
-        const size_t cl = rd32(d + i + 4);
-        if (i + 8 + cl > n) { msg = "truncated WebP chunk"; return CS_ERR_BAD_WEBP; }
-        const uint8_t *p = d + i + 8;
-        if (!memcmp(d + i, "VP8X", 4) && cl >= 10) { a.cw = rd24(p + 4) + 1; a.ch = rd24(p + 7) + 1; have_canvas = true; }
-        else if (!memcmp(d + i, "ANIM", 4) && cl >= 6) { a.background = rd32(p); a.loops = uint32_t(p[4]) | (uint32_t(p[5]) << 8); have_anim = true; }
-        else if (!memcmp(d + i, "ANMF", 4)) {
+    for (riff::Chunks c(d, n, riff::declared_end(d, n)); c.next();) {
+        if (c.truncated) { msg = "truncated WebP chunk"; return CS_ERR_BAD_WEBP; }
+        const uint8_t *p = c.payload();
+        const size_t cl = c.len;
+        if (c.is("VP8X") && cl >= 10) { a.cw = rd24(p + 4) + 1; a.ch = rd24(p + 7) + 1; have_canvas = true; }
+        else if (c.is("ANIM") && cl >= 6) { a.background = rd32(p); a.loops = uint32_t(p[4]) | (uint32_t(p[5]) << 8); have_anim = true; }
+        else if (c.is("ANMF")) {
             if (!have_canvas || !have_anim || cl < 16) { msg = "ANMF chunk without VP8X and ANIM in front of it, or shorter than its header"; return CS_ERR_BAD_WEBP; }
             csw::AnimFrame f;
             memset(&f, 0, sizeof f);
@@ -53,19 +44,17 @@ int cswd_parse_anim(const uint8_t *d, size_t n, cswd_anim &a, std::vector<cswd_f
             f.flags = ((p[15] & 0x01) ? csw::ANIM_DISPOSE : 0u) | ((p[15] & 0x02) ? csw::ANIM_NO_BLEND : 0u);
             if (uint64_t(f.x) + f.w > a.cw || uint64_t(f.y) + f.h > a.ch) { msg = "an animation frame leaves the canvas"; return CS_ERR_BAD_WEBP; }
             cswd_frame_src s;
-            for (size_t j = 16; j + 8 <= cl && !s.len;) {   // ALPH in front of VP8, or VP8L; anything else is passed by
-                const size_t sl = rd32(p + j + 4);
-                if (j + 8 + sl > cl) { msg = "truncated chunk inside an ANMF chunk"; return CS_ERR_BAD_WEBP; }
-                if (!memcmp(p + j, "ALPH", 4)) { if (!s.alph_len) { s.alph_off = i + 8 + j + 8; s.alph_len = sl; } }
-                else if (!memcmp(p + j, "VP8 ", 4)) { s.off = i + 8 + j + 8; s.len = sl; }
-                else if (!memcmp(p + j, "VP8L", 4)) { s.off = i + 8 + j + 8; s.len = sl; s.lossless = true; }
-                j += 8 + sl + (sl & 1);
+            for (riff::Chunks in(p, cl, cl, 16); !s.len && in.next();) {   // ALPH in front of VP8, or VP8L; anything else is passed by
+                if (in.truncated) { msg = "truncated chunk inside an ANMF chunk"; return CS_ERR_BAD_WEBP; }
+                const size_t off = c.at + 8 + in.at + 8;
+                if (in.is("ALPH")) { if (!s.alph_len) { s.alph_off = off; s.alph_len = in.len; } }
+                else if (in.is("VP8 ")) { s.off = off; s.len = in.len; }
+                else if (in.is("VP8L")) { s.off = off; s.len = in.len; s.lossless = true; }
             }
             if (!s.len) { msg = "an ANMF chunk holds no VP8 / VP8L bitstream"; return CS_ERR_BAD_WEBP; }
             f.image = uint32_t(a.frames.size());
             a.frames.push_back(f); a.duration.push_back(rd24(p + 12)); src.push_back(s);
         }
-        i += 8 + cl + (cl & 1);
     }
     if (a.frames.empty()) { msg = "an animated WebP file without frames"; return CS_ERR_BAD_WEBP; }
     if (uint64_t(a.cw) * a.ch > (uint64_t(1) << 30)) { msg = "animated WebP: a canvas of more than 2^30 pixels has no device path"; return CS_ERR_UNSUPPORTED; }
@@ -112,7 +101,7 @@ struct Chunks {   // a frame's coded chunks as they go into its ANMF: [ALPH,] VP
 // files[j] of the batch -> outputs / results at the same index as the file has in `sources` (the array cswd_batch_create was given)
 extern "C" int cswd_batch_encode_anim(cswd_batch *b, const CByteArray *sources, const size_t *files, size_t nfiles, const CCSParameters *p, int device, CByteArray *outputs, CCSResult *results) {
     if (!nfiles) return 0;
-    auto fail_all = [&](int code, const char *msg) { for (size_t j = 0; j < nfiles; j++) { outputs[files[j]].data = nullptr; outputs[files[j]].length = 0; results[files[j]] = make_res(uint32_t(code), msg); } return int(nfiles); };
+    auto fail_all = [&](int code, const char *msg) { for (size_t j = 0; j < nfiles; j++) { outputs[files[j]].data = nullptr; outputs[files[j]].length = 0; results[files[j]] = make_result(uint32_t(code), msg); } return int(nfiles); };
     if (!b->ran) return fail_all(-1, "cswd_batch_encode_anim: batch not run");
     if (hipSetDevice(b->device) != hipSuccess) return fail_all(CS_ERR_NO_DEVICE, "hipSetDevice failed");
     const bool lossless = p->webp_lossless;
@@ -167,7 +156,7 @@ extern "C" int cswd_batch_encode_anim(cswd_batch *b, const CByteArray *sources, 
         std::vector<csp_pixels> px(rn);
         std::vector<CByteArray> out(rn);
         std::vector<CCSResult> res(rn);
-        for (size_t k = 0; k < rn; k++) { const csw::AnimFrame &f = frames[r0 + k]; px[k] = csp_pixels{d_rects.p + f.out_off, f.ow, f.oh, lossless ? 4u : 3u}; out[k].data = nullptr; out[k].length = 0; res[k] = make_res(0, nullptr); }
+        for (size_t k = 0; k < rn; k++) { const csw::AnimFrame &f = frames[r0 + k]; px[k] = csp_pixels{d_rects.p + f.out_off, f.ow, f.oh, lossless ? 4u : 3u}; out[k].data = nullptr; out[k].length = 0; res[k] = make_result(0, nullptr); }
         if (lossless) csl_encode_pixels(px.data(), rn, device, out.data(), res.data());
         else {
             csh_batch *jb = nullptr;
@@ -175,25 +164,13 @@ extern "C" int cswd_batch_encode_anim(cswd_batch *b, const CByteArray *sources, 
             if (rc == 0) rc = csh_batch_run(jb, nullptr);
             if (rc == 0 && csh_batch_fetch(jb, out.data(), res.data()) < 0) rc = CS_ERR_NO_DEVICE;
             csh_batch_destroy(jb);
-            if (rc) for (size_t k = 0; k < rn; k++) { cs_free_bytes(&out[k]); cs_free_result(&res[k]); res[k] = make_res(uint32_t(rc), csh_last_error()); }
+            if (rc) for (size_t k = 0; k < rn; k++) { cs_free_bytes(&out[k]); cs_free_result(&res[k]); res[k] = make_result(uint32_t(rc), csh_last_error()); }
             // the alpha plane of a rectangle that is not opaque: the VP8L coder over it as a grey picture, into an ALPH chunk in front of the frame
             std::vector<csp_pixels> apx;
             std::vector<size_t> aat;
             for (size_t k = 0; k < rn; k++)
                 if (out[k].data && stats[(r0 + k) * csw::ANIM_STAT + 6]) { const csw::AnimFrame &f = frames[r0 + k]; apx.push_back(csp_pixels{d_rects.p + f.a_off, f.ow, f.oh, 1}); aat.push_back(k); }
-            if (!apx.empty()) {
-                std::vector<CByteArray> aout(apx.size());
-                std::vector<CCSResult> ares(apx.size());
-                csl_encode_pixels(apx.data(), apx.size(), device, aout.data(), ares.data());
-                for (size_t j = 0; j < apx.size(); j++) {
-                    const size_t k = aat[j];
-                    if (!aout[j].data || csl_attach_alpha(&out[k], &aout[j], apx[j].width, apx[j].height)) {
-                        cs_free_bytes(&out[k]); cs_free_result(&res[k]);
-                        res[k] = make_res(ares[j].code ? ares[j].code : CS_ERR_NO_DEVICE, "alpha plane coder failed");
-                    }
-                    cs_free_bytes(&aout[j]); cs_free_result(&ares[j]);
-                }
-            }
+            if (!apx.empty()) route::attach_alpha_planes(apx, aat, out.data(), res.data(), device);   // (a frame that fails here fails its file below)
         }
         for (size_t k = 0; k < rn; k++) {
             Chunks &c = coded[r0 + k];
@@ -223,30 +200,15 @@ extern "C" int cswd_batch_encode_anim(cswd_batch *b, const CByteArray *sources, 
             alpha |= coded[F.first + k].alpha;
             total += 8 + 16 + coded[F.first + k].bytes.size();
         }
-        if (bad) { results[at] = make_res(uint32_t(bad), bad_msg); failed++; continue; }
-        const uint8_t *icc = nullptr, *exif = nullptr;
-        size_t icc_len = 0, exif_len = 0;
-        if (p->keep_metadata) {   // what webp_carry_metadata carries for a still picture: the source's ICC profile and EXIF, not its XMP
-            const uint8_t *d = sources[at].data;
-            const size_t n = sources[at].length;
-            for (size_t i = 12; i + 8 <= n;) {
-                const size_t cl = rd32(d + i + 4);
-                if (i + 8 + cl > n) break;
-                if (!memcmp(d + i, "ICCP", 4) && !icc) { icc = d + i + 8; icc_len = cl; }
-                if (!memcmp(d + i, "EXIF", 4) && !exif) { exif = d + i + 8; exif_len = cl; }
-                i += 8 + cl + (cl & 1);
-            }
-        }
-        total += (icc ? 8 + icc_len + (icc_len & 1) : 0) + (exif ? 8 + exif_len + (exif_len & 1) : 0);
-        if (total > 0xFFFFFFF0ull) { results[at] = make_res(CS_ERR_UNSUPPORTED, "animated WebP output beyond the RIFF size field"); failed++; continue; }
-        uint8_t *o = static_cast<uint8_t *>(malloc(total)), *w = o;
-        if (!o) { results[at] = make_res(CS_ERR_NO_DEVICE, "out of memory"); failed++; continue; }
-        memcpy(w, "RIFF", 4); wr32(w + 4, uint32_t(total - 8)); memcpy(w + 8, "WEBPVP8X", 8); wr32(w + 16, 10);
-        w[20] = uint8_t(0x02 | (alpha ? 0x10 : 0) | (icc ? 0x20 : 0) | (exif ? 0x08 : 0)); w[21] = w[22] = w[23] = 0;
-        wr24(w + 24, a.cw - 1); wr24(w + 27, a.ch - 1);
-        w += 30;
-        auto chunk = [&](const char *id, const uint8_t *pl, size_t len) { memcpy(w, id, 4); wr32(w + 4, uint32_t(len)); memcpy(w + 8, pl, len); w += 8 + len; if (len & 1) *w++ = 0; };
-        if (icc) chunk("ICCP", icc, icc_len);
+        if (bad) { results[at] = make_result(uint32_t(bad), bad_msg); failed++; continue; }
+        // what a still picture keeps under keep_metadata (route_webp.cpp): the source's ICC profile and EXIF, not its XMP
+        const riff::Metadata md = p->keep_metadata ? riff::find_metadata(sources[at].data, sources[at].length) : riff::Metadata();
+        total += md.bytes();
+        if (total > 0xFFFFFFF0ull) { results[at] = make_result(CS_ERR_UNSUPPORTED, "animated WebP output beyond the RIFF size field"); failed++; continue; }
+        uint8_t *o = static_cast<uint8_t *>(malloc(total));
+        if (!o) { results[at] = make_result(CS_ERR_NO_DEVICE, "out of memory"); failed++; continue; }
+        uint8_t *w = riff::write_vp8x(riff::write_header(o, total), uint8_t(0x02 | (alpha ? 0x10 : 0) | md.vp8x_flags()), a.cw, a.ch);
+        if (md.icc) w = riff::append_chunk(w, "ICCP", md.icc, md.icc_len);
         memcpy(w, "ANIM", 4); wr32(w + 4, 6); wr32(w + 8, a.background); w[12] = uint8_t(a.loops); w[13] = uint8_t(a.loops >> 8); w += 14;
         for (uint32_t k = 0; k < F.nframes; k++) {
             const csw::AnimFrame &f = frames[F.first + k];
@@ -257,9 +219,9 @@ extern "C" int cswd_batch_encode_anim(cswd_batch *b, const CByteArray *sources, 
             memcpy(w + 24, c.data(), c.size());
             w += 24 + c.size();
         }
-        if (exif) chunk("EXIF", exif, exif_len);
+        if (md.exif) riff::append_chunk(w, "EXIF", md.exif, md.exif_len);
         outputs[at].data = o; outputs[at].length = total;
-        results[at] = make_res(0, nullptr);
+        results[at] = make_result(0, nullptr);
     }
     return failed;
 }

@@ -11,19 +11,18 @@
 #include <vector>
 
 #include "../../include/caesium_hip.h"
+#include "riff.h"
 #include "webp_anim.hpp"
 #include "vp8l_dec.h"
 
 using namespace csh;
-
-static uint32_t rd32le(const uint8_t *d) { return uint32_t(d[0]) | (uint32_t(d[1]) << 8) | (uint32_t(d[2]) << 16) | (uint32_t(d[3]) << 24); }
 
 enum { PARSE_ANIMATED = -2 };   // parse_webp: the file has ANIM / ANMF chunks (cswd_parse_anim takes it)
 // what a VP8 key frame / a VP8L stream says its size is
 static int frame_size(const uint8_t *f, size_t len, bool lossless, uint32_t &w, uint32_t &h, std::string &msg) {
     if (len < (lossless ? 5u : 10u)) { msg = "no VP8 frame in the WebP file"; return CS_ERR_BAD_WEBP; }
     if (lossless) {   // signature, 14 + 14 bits of size minus one, alpha hint, version
-        const uint32_t bits = rd32le(f + 1);
+        const uint32_t bits = riff::rd32(f + 1);
         if (f[0] != 0x2F || (bits >> 29) != 0) { msg = "malformed VP8L header"; return CS_ERR_BAD_WEBP; }
         w = (bits & 0x3FFFu) + 1; h = ((bits >> 14) & 0x3FFFu) + 1;
         return 0;
@@ -37,17 +36,13 @@ static int frame_size(const uint8_t *f, size_t len, bool lossless, uint32_t &w, 
 static int parse_webp(const uint8_t *d, size_t n, size_t &off, size_t &len, uint32_t &w, uint32_t &h, bool &lossless, size_t &alph_off, size_t &alph_len, std::string &msg) {
     lossless = false; alph_off = 0; alph_len = 0;
     if (n < 20 || memcmp(d, "RIFF", 4) || memcmp(d + 8, "WEBP", 4)) { msg = "not a WebP file"; return CS_ERR_UNKNOWN_TYPE; }
-    size_t end = size_t(rd32le(d + 4)) + 8;
-    if (end > n) end = n;   // libwebp tolerates a RIFF size past the file's end as long as the chunks are there
     bool found = false;
-    for (size_t i = 12; i + 8 <= end;) {
-        const size_t cl = rd32le(d + i + 4);
-        if (i + 8 + cl > n) { msg = "truncated WebP chunk"; return CS_ERR_BAD_WEBP; }
-        if (!memcmp(d + i, "VP8 ", 4)) { if (!found) { off = i + 8; len = cl; found = true; } }
-        else if (!memcmp(d + i, "VP8L", 4)) { if (!found) { off = i + 8; len = cl; found = true; lossless = true; } }
-        else if (!memcmp(d + i, "ALPH", 4)) { if (!found && !alph_len) { alph_off = i + 8; alph_len = cl; } }   // the alpha plane of the VP8 frame that follows
-        else if (!memcmp(d + i, "ANIM", 4) || !memcmp(d + i, "ANMF", 4)) return PARSE_ANIMATED;
-        i += 8 + cl + (cl & 1);
+    for (riff::Chunks c(d, n, riff::declared_end(d, n)); c.next();) {
+        if (c.truncated) { msg = "truncated WebP chunk"; return CS_ERR_BAD_WEBP; }
+        if (c.is("VP8 ")) { if (!found) { off = c.at + 8; len = c.len; found = true; } }
+        else if (c.is("VP8L")) { if (!found) { off = c.at + 8; len = c.len; found = true; lossless = true; } }
+        else if (c.is("ALPH")) { if (!found && !alph_len) { alph_off = c.at + 8; alph_len = c.len; } }   // the alpha plane of the VP8 frame that follows
+        else if (c.is("ANIM") || c.is("ANMF")) return PARSE_ANIMATED;
     }
     if (!found) { msg = "no VP8 frame in the WebP file"; return CS_ERR_BAD_WEBP; }
     if (lossless) alph_len = 0;
