@@ -73,6 +73,7 @@ struct PixelPlan {
     uint64_t plane_bytes = 0, oplane_bytes = 0;
     uint32_t max_quads = 0;
     bool any_layout = false, any_layout_rgb = false;   // some work item is CSH_MODE_ANY / some resize item CSH_RZ_ANY: the batch launches k_resample_any / k_planes_to_rgb_any
+    bool any_space_rgb = false;                        // some resize item is CSH_RZ_SPACE: the batch launches k_planes_to_rgb_space
 
     DevBuf<uint8_t> d_planes, d_oplanes, d_rgb;
     DevBuf<PlaneWork> d_pwork;
@@ -94,6 +95,7 @@ struct SearchImg {
     uint64_t best_luma = 0, best_chroma = 0;   // running minimum of the decision in progress
     int split_luma = 0, split_chroma = 0;
     bool luma_on = false, chroma_on = false;    // the decision in progress needs the next stage's candidates
+    bool fixed = false;                         // an RGB / CMYK / YCCK frame: no search (mozjpeg's jpeg_search_progression declines), its list of scans stands from the start
 };
 
 // phases 2..6: tokens, lists, tables, sizes, packing, assembly (k_entropy.hip, k_aclist.hip, k_assemble.hip) and the scan search's stages
@@ -339,6 +341,7 @@ struct BatchPlanner {
     const bool progressive;
     uint16_t qout_nat[64];
     int script_base3 = 0, script_base1 = 0;
+    std::map<int, int> other_scripts;   // CSH_CS_RGB / CMYK / YCCK -> first EncScan of the frame's stock script
     std::vector<std::pair<std::vector<uint8_t>, int>> hset_keys;
     std::map<std::vector<uint16_t>, int> quant_index;
     uint64_t plane_off = 64, oplane_off = 0;  // 64-bit: a resize batch of 1024 1080p files has 7 GB of planes; 64 bytes in front of the first plane: k_resample_fdct_420 reads a row's window from four bytes before it
@@ -365,9 +368,10 @@ private:
     void output_scans(Item &it, ImgDesc &im, int img_index, size_t in_len);
     void frame_header(Item &it);
     template <class Fill> int enc_scan(const std::array<int, 5> &key, Fill fill);
-    int cand_index(int comp, int Ss, int Se, int Ah, int Al);
+    int space_script(int ncomp, int space, int &ns);
+    int cand_index(int comp, int Ss, int Se, int Ah, int Al, int cls = -1);
     int dc_scan_index(int ncomp);
-    int seq1_index(int comp);
+    int seq1_index(int comp, int cls = -1);
     uint32_t nz_list(int img_index, int comp, int Al, const ImgDesc &im, size_t in_len);
     void add_works(Item &it, ImgDesc &im, int img_index, const std::vector<int> &list, size_t in_len, const JpegInfo &o, bool stats_only = false);
     template <class Make> void add_stage(int sid, Make make);

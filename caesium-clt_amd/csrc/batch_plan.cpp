@@ -97,9 +97,10 @@ static void fill_geom(const JComp &c, CompGeom &g, uint32_t &ntiles) {
 }
 
 // output script -> EncScan entries (progressive: libjpeg jpeg_simple_progression; sequential: one interleaved scan).
-// Y uses Huffman table ids 0, chroma ids 1.
-static void add_script(std::vector<EncScan> &v, int ncomp, bool progressive) {
-    for (const OutScan &o : output_script(ncomp, progressive)) {
+// A component's Huffman table ids are its libjpeg table number in the frame's colour space (table_class): Y 0 and chroma 1; R, G, B and
+// C, M, Y, K all 0; of YCCK, Y and K 0, Cb and Cr 1.
+static void add_script(std::vector<EncScan> &v, int ncomp, bool progressive, int space) {
+    for (const OutScan &o : output_script(ncomp, progressive, space == CSH_CS_YCC)) {
         EncScan e;
         memset(&e, 0, sizeof e);
         e.ncomp = o.ncomp; e.Ss = o.Ss; e.Se = o.Se; e.Ah = o.Ah; e.Al = o.Al;
@@ -107,7 +108,7 @@ static void add_script(std::vector<EncScan> &v, int ncomp, bool progressive) {
         if (!progressive) {
             e.sequential = 1;
             for (int k = 0; k < o.ncomp; k++) {   // DHT order: per component DC then AC, each table once (libjpeg write_scan_header)
-                int id = o.comp[k] ? 1 : 0;
+                int id = table_class(space, o.comp[k]);
                 int di = -1, ai = -1;
                 for (int t = 0; t < e.ntables; t++) { if (e.dht_id[t] == id) di = t; if (e.dht_id[t] == (0x10 | id)) ai = t; }
                 if (di < 0) { di = e.ntables; e.dht_id[e.ntables++] = id; }
@@ -119,7 +120,7 @@ static void add_script(std::vector<EncScan> &v, int ncomp, bool progressive) {
             if (o.Ah == 0) {
                 e.ntables = 0;
                 for (int k = 0; k < o.ncomp; k++) {
-                    int id = o.comp[k] ? 1 : 0;
+                    int id = table_class(space, o.comp[k]);
                     int idx = -1;
                     for (int t = 0; t < e.ntables; t++) if (e.dht_id[t] == id) idx = t;
                     if (idx < 0) { idx = e.ntables; e.dht_id[e.ntables++] = id; }
@@ -128,7 +129,7 @@ static void add_script(std::vector<EncScan> &v, int ncomp, bool progressive) {
                 }
             }
         } else {
-            int id = o.comp[0] ? 1 : 0;
+            int id = table_class(space, o.comp[0]);
             e.ntables = 1; e.dht_id[0] = 0x10 | id; e.sos_tdta[0] = id;
         }
         v.push_back(e);
@@ -148,24 +149,37 @@ static UpDesc up_desc(int hx, int vx, int cw) {
 // full resolution -> encoder plane (jcsample.c): the output layouts are 4:4:4, 4:2:2, 4:2:0 and 4:1:1 (plan_item)
 static int dn_kind(int hx, int vx) { return hx == 1 ? CSH_DN_FULL : (hx == 4 ? CSH_DN_H4V1 : (vx == 2 ? CSH_DN_H2V2 : CSH_DN_H2V1)); }
 
-// decide the output frame for one parsed JPEG; returns 0 or an error code
-static int plan_item(Item &it, const CCSParameters &p, bool lossless) {
+// decide the output frame for one parsed JPEG; returns 0 or an error code.  to_rgb: the run goes through the image's RGB (a resize, WebP or
+// pixel output): an RGB / CMYK / YCCK source is converted there (k_planes_to_rgb_space) and what follows is an ordinary three-component image
+static int plan_item(Item &it, const CCSParameters &p, bool lossless, bool to_rgb) {
     const JpegInfo &in = it.in;
-    if (in.ncomp != 1 && in.ncomp != 3) { it.msg = "unsupported component count (CMYK/YCCK not on the device path yet)"; return CS_ERR_JPEG_FEATURE; }
-    if (in.ncomp == 3) {
-        bool rgb_ids = in.comp[0].id == 'R' && in.comp[1].id == 'G' && in.comp[2].id == 'B';
-        if (in.adobe_transform == 0 || rgb_ids) { it.msg = "RGB-colourspace JPEG not on the device path yet"; return CS_ERR_JPEG_FEATURE; }
-    }
+    if (in.ncomp != 1 && in.ncomp != 3 && in.ncomp != 4) { it.msg = "unsupported component count"; return CS_ERR_JPEG_FEATURE; }
     // one image's planes, tiles and unit arrays are indexed with 32 bits and take ~25 bytes per pixel of HBM: a header that declares
     // more than 2^28 pixels (16384 x 16384) fails here, by itself, instead of sizing the whole batch's pools
     if (uint64_t(in.width) * uint64_t(in.height) > (1ull << 28)) { it.msg = "image dimensions too large for the device path"; return CS_ERR_JPEG_FEATURE; }
+    const bool other_space = in.space != CSH_CS_GREY && in.space != CSH_CS_YCC;   // RGB, CMYK, YCCK: coded in their own space (mozjpeg with out_color_space = jpeg_color_space)
+    const bool converted = other_space && to_rgb;
     it.out = JpegInfo();
     JpegInfo &o = it.out;
-    o.width = in.width; o.height = in.height; o.ncomp = in.ncomp;
+    o.width = in.width; o.height = in.height; o.ncomp = converted ? 3 : in.ncomp;
+    o.space = converted ? CSH_CS_YCC : in.space;
+    if (other_space && !converted) { o.write_jfif = false; o.write_adobe = in.adobe_transform; }   // the Adobe segment exactly when the source has one, with its transform
     if (p.width || p.height) {
         if (lossless) { it.msg = "resize + lossless transcode not on the device path"; return CS_ERR_UNSUPPORTED; }
         csh_compute_dimensions(in.width, in.height, int(p.width), int(p.height), o.width, o.height);
         if (o.width > 65500 || o.height > 65500 || uint64_t(o.width) * uint64_t(o.height) > (1ull << 28)) { it.msg = "resize target too large for JPEG"; return CS_ERR_JPEG_FEATURE; }
+    }
+    if (in.ncomp >= 3 && (!lossless || in.ncomp == 4)) {
+        // any layout libjpeg decodes: every component's up factors hmax / h and vmax / v integers in 1..4 (jdsample.c int_upsample), at most
+        // 10 blocks per MCU (D_MAX_BLOCKS_IN_MCU)
+        int blocks = 0;
+        for (int c = 0; c < in.ncomp; c++) {
+            const JComp &k = in.comp[c];
+            blocks += k.h * k.v;
+            if (in.hmax % k.h || in.vmax % k.v) { it.msg = "fractional chroma sampling ratio (component factors do not divide the largest ones)"; return CS_ERR_JPEG_FEATURE; }
+            if (in.hmax / k.h > 4 || in.vmax / k.v > 4) { it.msg = "chroma sampling ratio above 4"; return CS_ERR_JPEG_FEATURE; }
+        }
+        if (blocks > 10) { it.msg = "more than 10 blocks per MCU"; return CS_ERR_JPEG_FEATURE; }
     }
     if (lossless) {
         // the output carries the slots as the file leaves them (frame_header): a component decoded with other contents cannot be
@@ -178,22 +192,21 @@ static int plan_item(Item &it, const CCSParameters &p, bool lossless) {
     }
     int ss = int(p.jpeg_chroma_subsampling);
     if (ss == 0) ss = 420;
-    for (int c = 0; c < in.ncomp; c++) { o.comp[c].id = c + 1; o.comp[c].h = o.comp[c].v = 1; o.comp[c].tq = c ? 1 : 0; }
-    if (in.ncomp == 3) {
-        // any layout libjpeg decodes: every component's up factors hmax / h and vmax / v integers in 1..4 (jdsample.c int_upsample), at most
-        // 10 blocks per MCU (D_MAX_BLOCKS_IN_MCU)
-        int blocks = 0;
-        for (int c = 0; c < 3; c++) {
-            const JComp &k = in.comp[c];
-            blocks += k.h * k.v;
-            if (in.hmax % k.h || in.vmax % k.v) { it.msg = "fractional chroma sampling ratio (component factors do not divide the largest ones)"; return CS_ERR_JPEG_FEATURE; }
-            if (in.hmax / k.h > 4 || in.vmax / k.v > 4) { it.msg = "chroma sampling ratio above 4"; return CS_ERR_JPEG_FEATURE; }
-        }
-        if (blocks > 10) { it.msg = "more than 10 blocks per MCU"; return CS_ERR_JPEG_FEATURE; }
-        if (ss == 420) { o.comp[0].h = 2; o.comp[0].v = 2; }
-        else if (ss == 422) { o.comp[0].h = 2; o.comp[0].v = 1; }
-        else if (ss == 411) { o.comp[0].h = 4; o.comp[0].v = 1; }
+    // libjpeg jpeg_set_colorspace: ids 1.. (R G B / C M Y K by letter), every component 1x1, the table number of its class
+    static const char kRgbIds[] = "RGB", kCmykIds[] = "CMYK";
+    for (int c = 0; c < o.ncomp; c++) {
+        o.comp[c].id = o.space == CSH_CS_RGB ? kRgbIds[c] : (o.space == CSH_CS_CMYK ? kCmykIds[c] : c + 1);
+        o.comp[c].h = o.comp[c].v = 1; o.comp[c].tq = table_class(o.space, c);
+    }
+    // the subsampling setting shapes YCbCr and YCCK frames (K follows Y); R, G, B and C, M, Y, K stay at full resolution
+    if (o.space == CSH_CS_YCC || o.space == CSH_CS_YCCK) {
+        int h = 1, v = 1;
+        if (ss == 420) { h = 2; v = 2; }
+        else if (ss == 422) { h = 2; v = 1; }
+        else if (ss == 411) { h = 4; v = 1; }
         else if (ss != 444) { it.msg = "unknown output chroma subsampling"; return CS_ERR_JPEG_FEATURE; }
+        o.comp[0].h = h; o.comp[0].v = v;
+        if (o.space == CSH_CS_YCCK) { o.comp[3].h = h; o.comp[3].v = v; }
     }
     jpeg_geometry(o);
     return 0;
@@ -265,11 +278,11 @@ void BatchPlanner::begin() {
     b->enc.list_run = sw.list_run;
     b->enc.ac_runs_slot = sw.ac_runs_slot;
 
-    add_script(b->enc.script, 3, true);   // entries 0..9
-    add_script(b->enc.script, 1, true);   // entries 10..15
-    add_script(b->enc.script, 3, false);  // entry 16
-    add_script(b->enc.script, 1, false);  // entry 17
-    script_base3 = progressive ? 0 : 16; script_base1 = progressive ? 10 : 17;
+    add_script(b->enc.script, 3, true, CSH_CS_YCC);    // entries 0..9
+    add_script(b->enc.script, 1, true, CSH_CS_GREY);   // entries 10..15
+    add_script(b->enc.script, 3, false, CSH_CS_YCC);   // entry 16
+    add_script(b->enc.script, 1, false, CSH_CS_GREY);  // entry 17
+    script_base3 = progressive ? 0 : 16; script_base1 = progressive ? 10 : 17;   // (the scripts of RGB, CMYK and YCCK frames: space_script, on first use)
     // CSH_PROFILE names what stands in for libcaesium's JPEG engine.  Unset or "mozjpeg": the whole JCP_MAX_COMPRESSION profile libcaesium's
     // -q runs (compressor.rs:415,427): scan search + trellis quantisation + overshoot deringing.  "scalar": the scan search over the scalar
     // quantiser (the pieces pinned by samples/j0.JPG and libjpeg-turbo); "plain": the stock jpeg_simple_progression script over the
@@ -295,9 +308,24 @@ int BatchPlanner::enc_scan(const std::array<int, 5> &key, Fill fill) {
     b->enc.script.push_back(e);
     return b->enc.cand_script[key] = int(b->enc.script.size()) - 1;
 }
-int BatchPlanner::cand_index(int comp, int Ss, int Se, int Ah, int Al) {
-    return enc_scan({comp, Ss, Se, Ah, Al}, [&](EncScan &e) {
-        const int id = comp ? 1 : 0;
+// the stock script of a frame in `space`: its first EncScan and the number of them
+int BatchPlanner::space_script(int ncomp, int space, int &ns) {
+    ns = progressive ? (space == CSH_CS_YCC ? 10 : 2 + 4 * ncomp) : 1;
+    if (space == CSH_CS_YCC) return script_base3;
+    if (space == CSH_CS_GREY) return script_base1;
+    auto f = other_scripts.find(space);
+    if (f == other_scripts.end()) {
+        f = other_scripts.emplace(space, int(b->enc.script.size())).first;
+        add_script(b->enc.script, ncomp, progressive, space);
+    }
+    return f->second;
+}
+// cls: the component's table number (table_class); a key of its own where it is not the YCbCr one, so that component 1 of an RGB frame and Cb do not share an entry
+int BatchPlanner::cand_index(int comp, int Ss, int Se, int Ah, int Al, int cls) {
+    const int ycc = comp ? 1 : 0;
+    if (cls < 0) cls = ycc;
+    return enc_scan({cls == ycc ? comp : comp + 16 * (1 + cls), Ss, Se, Ah, Al}, [&](EncScan &e) {
+        const int id = cls;
         e.ncomp = 1; e.comp[0] = comp; e.Ss = Ss; e.Se = Se; e.Ah = Ah; e.Al = Al;
         e.ntables = 1; e.dht_id[0] = 0x10 | id; e.sos_tdta[0] = id;
     });
@@ -315,9 +343,11 @@ int BatchPlanner::dc_scan_index(int ncomp) {   // first DC scan of all component
         }
     });
 }
-int BatchPlanner::seq1_index(int comp) {   // a one-component sequential scan (the trellis stage's statistics scan of a sequential output)
-    return enc_scan({comp, 0, 63, -1, -1}, [&](EncScan &e) {
-        const int id = comp ? 1 : 0;
+int BatchPlanner::seq1_index(int comp, int cls) {   // a one-component sequential scan (the trellis stage's statistics scan of a sequential output)
+    const int ycc = comp ? 1 : 0;
+    if (cls < 0) cls = ycc;
+    return enc_scan({cls == ycc ? comp : comp + 16 * (1 + cls), 0, 63, -1, -1}, [&](EncScan &e) {
+        const int id = cls;
         e.ncomp = 1; e.comp[0] = comp; e.Ss = 0; e.Se = 63; e.sequential = 1;
         e.ntables = 2; e.dht_id[0] = id; e.dht_id[1] = 0x10 | id; e.dc_tbl[0] = 0; e.ac_tbl[0] = 1; e.sos_tdta[0] = (id << 4) | id;
     });
@@ -506,14 +536,11 @@ int BatchPlanner::reserve_pinned() {
 // geometry of the decoded and the encoded image, the source's quantisation tables (de-duplicated by content)
 void BatchPlanner::image_geometry(Item &it, ImgDesc &im) {
     const JpegInfo &in = it.in, &o = it.out;
-    im.width = in.width; im.height = in.height; im.ncomp = in.ncomp;
+    im.width = in.width; im.height = in.height; im.ncomp = o.ncomp; im.ncomp_in = in.ncomp;
     im.mcus_x = in.mcus_x; im.mcus_y = in.mcus_y;
     im.progressive_in = in.progressive;
-    for (int c = 0; c < in.ncomp; c++) fill_geom(in.comp[c], im.in[c], b->ntiles_in);
     for (int c = 0; c < in.ncomp; c++) {
-        if (b->lossless) im.out[c] = im.in[c];
-        else fill_geom(o.comp[c], im.out[c], b->ntiles_out);  // rebased behind all decoded tiles below
-        im.comp_id[c] = o.comp[c].id;
+        fill_geom(in.comp[c], im.in[c], b->ntiles_in);
         std::vector<uint16_t> key(in.comp[c].qt, in.comp[c].qt + 64);
         auto f = quant_index.find(key);
         if (f == quant_index.end()) {
@@ -522,8 +549,14 @@ void BatchPlanner::image_geometry(Item &it, ImgDesc &im) {
             b->quants.push_back(q);
         }
         im.qt_in[c] = f->second;
+        b->max_tiles = std::max<uint32_t>(b->max_tiles, im.in[c].ntiles);
+    }
+    for (int c = 0; c < o.ncomp; c++) {
+        if (b->lossless) im.out[c] = im.in[c];
+        else fill_geom(o.comp[c], im.out[c], b->ntiles_out);  // rebased behind all decoded tiles below
+        im.comp_id[c] = o.comp[c].id;
         im.qt_out[c] = 0;
-        b->max_tiles = std::max<uint32_t>(b->max_tiles, std::max(im.in[c].ntiles, im.out[c].ntiles));
+        b->max_tiles = std::max<uint32_t>(b->max_tiles, im.out[c].ntiles);
         uint32_t nd = uint32_t(im.out[c].bw * im.out[c].bh - im.out[c].real_bw * im.out[c].real_bh);
         b->max_dummy = std::max(b->max_dummy, nd);
     }
@@ -796,6 +829,14 @@ bool BatchPlanner::progressive_plan(const Item &it, const ImgDesc &im, int img_i
 void BatchPlanner::plane_work(ImgDesc &im, const JpegInfo &in, const JpegInfo &o, int img_index, bool resized) {
     for (int c = 0; c < in.ncomp; c++) {
         PlaneWork w; w.image = img_index; w.comp = c; w.nzset = 0xFFFFFFFFu; w.ac_lists = 0u;   // (finish_descriptors names the set: the lists are planned behind the pixel work)
+        if (c >= o.ncomp) {   // K of a CMYK / YCCK source that is converted: its plane feeds k_planes_to_rgb_space, the output frame has three components
+            w.up = up_desc(1, 1, 0); w.dn = CSH_DN_FULL; w.mode = CSH_MODE_DECODE;
+            im.plane_off[c] = plane_off;
+            plane_off += uint64_t(im.in[c].real_bw * 8) * uint64_t(im.in[c].real_bh * 8);
+            plane_off = (plane_off + 63u) & ~uint64_t(63);
+            b->pix.pwork.push_back(w);
+            continue;
+        }
         w.up = resized ? up_desc(1, 1, 0) : up_desc(in.hmax / in.comp[c].h, in.vmax / in.comp[c].v, in.comp[c].comp_w);
         w.dn = dn_kind(o.hmax / o.comp[c].h, o.vmax / o.comp[c].v);
         // the layouts k_resample_plane takes keep its mode numbers (in: 0 full, 1 h2v2, 2 h2v1 by the up factors); every other one is CSH_MODE_ANY
@@ -836,31 +877,35 @@ void BatchPlanner::resize_work(const JpegInfo &in, const JpegInfo &o, int img_in
     rw.image = img_index; rw.nw = o.width; rw.nh = o.height;
     rw.in_kind = in.ncomp == 1 ? 0 : ((in.comp[1].h == in.hmax && in.comp[1].v == in.vmax) ? 0 : (in.comp[1].v == in.vmax ? 2 : 1));
     for (int c = 0; c < in.ncomp; c++) rw.up[c] = up_desc(in.hmax / in.comp[c].h, in.vmax / in.comp[c].v, in.comp[c].comp_w);
-    if (in.ncomp == 3) {   // k_planes_to_rgb takes full luma and Cb, Cr both 1x1 (full), 2x2 or 2x1 below it
+    const int nc = o.ncomp;   // samples per pixel of the image's RGB
+    if (in.space != CSH_CS_GREY && in.space != CSH_CS_YCC) {   // planes in another colour space: k_planes_to_rgb_space
+        rw.in_kind = CSH_RZ_SPACE; rw.space = in.space;
+        b->pix.any_space_rgb = true;
+    } else if (in.ncomp == 3) {   // k_planes_to_rgb takes full luma and Cb, Cr both 1x1 (full), 2x2 or 2x1 below it
         auto same = [&](int c, int hx, int vx) { return rw.up[c].hx == hx && rw.up[c].vx == vx; };
         const bool legacy = same(0, 1, 1) && rw.up[1].hx == rw.up[2].hx && rw.up[1].vx == rw.up[2].vx &&
                             (same(1, 1, 1) || same(1, 2, 2) || same(1, 2, 1));
         if (!legacy) { rw.in_kind = CSH_RZ_ANY; b->pix.any_layout_rgb = true; }
     }
     if (px) rw.in_kind = -1;   // the RGB of this image is not made from decoded planes: it is copied in below (csh_batch_create_from_pixels)
-    const uint64_t src_bytes = uint64_t(in.width) * in.height * in.ncomp, dst_bytes = uint64_t(o.width) * o.height * in.ncomp;
+    const uint64_t src_bytes = uint64_t(in.width) * in.height * nc, dst_bytes = uint64_t(o.width) * o.height * nc;
     rw.rgb_src_off = b->pix.rgb_bytes; b->pix.rgb_bytes += (src_bytes + 63) & ~uint64_t(63);
     rw.rgb_dst_off = b->pix.rgb_bytes; b->pix.rgb_bytes += (dst_bytes + 63) & ~uint64_t(63);
-    const uint64_t tmpn = uint64_t(o.height) * in.width * in.ncomp;
+    const uint64_t tmpn = uint64_t(o.height) * in.width * nc;
     rw.tmp_off = b->pix.tmp_floats; b->pix.tmp_floats += tmpn;
     const bool same = o.width == in.width && o.height == in.height;   // image-rs copies instead of resampling
     rw.vtap_base = uint32_t(b->pix.rtaps.size()); csh_lanczos_axis(in.height, o.height, same, b->pix.rtaps, b->pix.rweights);
     rw.htap_base = uint32_t(b->pix.rtaps.size()); csh_lanczos_axis(in.width, o.width, same, b->pix.rtaps, b->pix.rweights);
     b->pix.max_src_px = std::max<uint32_t>(b->pix.max_src_px, uint32_t(in.width) * in.height);
     b->pix.max_tmp = std::max(b->pix.max_tmp, tmpn);
-    b->pix.max_row_in = std::max(b->pix.max_row_in, uint32_t(in.width) * uint32_t(in.ncomp)); b->pix.max_out_w = std::max(b->pix.max_out_w, uint32_t(o.width));
+    b->pix.max_row_in = std::max(b->pix.max_row_in, uint32_t(in.width) * uint32_t(nc)); b->pix.max_out_w = std::max(b->pix.max_out_w, uint32_t(o.width));
     b->pix.max_nh = std::max(b->pix.max_nh, uint32_t(o.height));
     b->pix.max_dst = std::max(b->pix.max_dst, dst_bytes);
     b->pix.rwork.push_back(rw);
     if (b->webp) {
         csw::WebpImg wi;
         memset(&wi, 0, sizeof wi);
-        wi.width = uint32_t(o.width); wi.height = uint32_t(o.height); wi.mbw = (wi.width + 15) / 16; wi.mbh = (wi.height + 15) / 16; wi.ncomp = uint32_t(in.ncomp);
+        wi.width = uint32_t(o.width); wi.height = uint32_t(o.height); wi.mbw = (wi.width + 15) / 16; wi.mbh = (wi.height + 15) / 16; wi.ncomp = uint32_t(nc);
         wi.rgb_off = rw.rgb_dst_off; wi.image = uint32_t(img_index);
         const uint64_t ly = uint64_t(wi.mbw) * wi.mbh * 256, lc = uint64_t(wi.mbw) * wi.mbh * 64;
         auto take = [&](uint64_t n) { uint64_t at = b->wp.wwork_bytes; b->wp.wwork_bytes += (n + 63) & ~uint64_t(63); return at; };
@@ -874,28 +919,35 @@ void BatchPlanner::resize_work(const JpegInfo &in, const JpegInfo &o, int img_in
 
 // output scans: the plain script, or stage 1 of the search
 void BatchPlanner::output_scans(Item &it, ImgDesc &im, int img_index, size_t in_len) {
-    const JpegInfo &in = it.in, &o = it.out;
+    const JpegInfo &o = it.out;
     im.first_work = int(b->enc.swork.size());
-    if (!b->enc.search) {
-        int sb = in.ncomp == 3 ? script_base3 : script_base1;
-        int ns = progressive ? (in.ncomp == 3 ? 10 : 6) : 1;
+    const bool fixed = o.space != CSH_CS_GREY && o.space != CSH_CS_YCC;   // RGB, CMYK, YCCK: the stock script, whatever the profile
+    if (!b->enc.search || fixed) {
+        int ns = 0;
+        const int sb = space_script(o.ncomp, o.space, ns);
         std::vector<int> list;
         for (int s = 0; s < ns; s++) list.push_back(sb + s);
         add_works(it, im, img_index, list, in_len, o);
         for (int s = 0; s < ns; s++) b->enc.img_list.push_back(uint32_t(im.first_work + s));
         b->enc.img_list.resize(size_t(img_index + 1) * CSH_LIST_MAX, 0u);
         b->enc.img_nlist.push_back(uint32_t(ns));
+        if (b->enc.search) {   // among searched images: nothing to decide, no later stage
+            SearchImg si;
+            for (int &cw : si.cand_work) cw = -1;
+            si.ncand = 0; si.fixed = true;
+            b->enc.simg.push_back(si);
+        }
     } else {
         // stage 1 of the search: the DC scan and every candidate whose Al is fixed (oracle/jpeg_oracle.c cso_search_progression)
         SearchImg si;
         for (int &cw : si.cand_work) cw = -1;
         std::vector<int> list, cands;
         auto add = [&](int cand, int idx) { cands.push_back(cand); list.push_back(idx); };
-        add(0, dc_scan_index(in.ncomp));
+        add(0, dc_scan_index(o.ncomp));
         add(1, cand_index(0, 1, 8, 0, 0)); add(2, cand_index(0, 9, 63, 0, 0));
         // luma at Al 1 and 2 (mozjpeg tries Al 3 only when Al 2 beat Al 1: candidates 9-11 are stage ST_1B)
         for (int Al = 0; Al < 2; Al++) { add(3 + 3 * Al, cand_index(0, 1, 63, Al + 1, Al)); add(4 + 3 * Al, cand_index(0, 1, 8, 0, Al + 1)); add(5 + 3 * Al, cand_index(0, 9, 63, 0, Al + 1)); }
-        if (in.ncomp == 3) {
+        if (o.ncomp == 3) {
             add(26, cand_index(1, 1, 8, 0, 0)); add(27, cand_index(1, 9, 63, 0, 0)); add(28, cand_index(2, 1, 8, 0, 0)); add(29, cand_index(2, 9, 63, 0, 0));
             for (int Al = 0; Al < 2; Al++) {
                 add(30 + 6 * Al, cand_index(1, 1, 63, Al + 1, Al)); add(31 + 6 * Al, cand_index(2, 1, 63, Al + 1, Al));
@@ -905,7 +957,7 @@ void BatchPlanner::output_scans(Item &it, ImgDesc &im, int img_index, size_t in_
         }
         add_works(it, im, img_index, list, in_len, o);
         for (size_t k = 0; k < cands.size(); k++) si.cand_work[cands[k]] = im.first_work + int(k);
-        si.ncand = in.ncomp == 3 ? 64 : 23;
+        si.ncand = o.ncomp == 3 ? 64 : 23;
         b->enc.simg.push_back(si);
         b->enc.img_list.resize(size_t(img_index + 1) * CSH_LIST_MAX, 0u);
         b->enc.img_nlist.push_back(0u);
@@ -925,6 +977,9 @@ void BatchPlanner::frame_header(Item &it) {
     for (size_t mo = 0; mo + 4 <= in.meta.size();) {
         size_t L = (size_t(in.meta[mo + 2]) << 8) | in.meta[mo + 3];
         bool is_icc = in.meta[mo + 1] == 0xE2 && L >= 14 && !memcmp(&in.meta[mo + 4], "ICC_PROFILE\0", 12);
+        const bool is_adobe = in.meta[mo + 1] == 0xEE && L >= 14 && !memcmp(&in.meta[mo + 4], "Adobe", 5);
+        // an RGB / CMYK / YCCK source: a frame in the source's space writes the segment itself (build_frame_header), a converted one is YCbCr and must not carry it
+        if (is_adobe && in.space != CSH_CS_GREY && in.space != CSH_CS_YCC) { mo += 2 + L; continue; }
         if (is_icc ? p->jpeg_preserve_icc : p->keep_metadata) meta.insert(meta.end(), in.meta.begin() + mo, in.meta.begin() + mo + 2 + L);
         mo += 2 + L;
     }
@@ -939,7 +994,8 @@ int BatchPlanner::plan_image(size_t n) {
     Item &it = b->items[n];
     const uint8_t *d = inputs[n].data;
     if (it.code) return 0;
-    it.code = plan_item(it, *p, b->lossless);
+    const bool to_rgb = ((p->width || p->height) && !b->lossless) || b->webp || b->rgb_out || px;
+    it.code = plan_item(it, *p, b->lossless, to_rgb);
     if (it.code) return 0;
 
     ImgDesc im;
@@ -947,7 +1003,7 @@ int BatchPlanner::plan_image(size_t n) {
     const JpegInfo &in = it.in, &o = it.out;
     const int img_index = int(b->imgs.size());
     image_geometry(it, im);
-    const bool resized = ((p->width || p->height) && !b->lossless) || b->webp || b->rgb_out || px;   // the WebP encoder takes the RGB the resize branch produces (a plain copy at equal size)
+    const bool resized = to_rgb;   // the WebP encoder takes the RGB the resize branch produces (a plain copy at equal size)
     if (int rc = decode_scans(it, im, d)) return rc;
     if (it.code) { b->dec.dscans.resize(im.first_scan); return 0; }
     bool par_ok = false;
@@ -978,6 +1034,7 @@ void BatchPlanner::add_stage(int sid, Make make) {
         if (it.image < 0) continue;
         ImgDesc &im = b->imgs[size_t(it.image)];
         SearchImg &si = b->enc.simg[size_t(it.image)];
+        if (si.fixed) continue;
         std::vector<int> list, cands;
         auto add = [&](int cand, int idx) { cands.push_back(cand); list.push_back(idx); };
         make(im, add);
@@ -1034,14 +1091,15 @@ int BatchPlanner::plan_trellis() {
         if (it.image < 0) continue;
         ImgDesc &im = b->imgs[size_t(it.image)];
         std::vector<int> list;
-        for (int c = 0; c < im.ncomp; c++) list.push_back(progressive ? cand_index(c, 1, 63, 0, 0) : seq1_index(c));
+        const int space = it.out.space;
+        for (int c = 0; c < im.ncomp; c++) list.push_back(progressive ? cand_index(c, 1, 63, 0, 0, table_class(space, c)) : seq1_index(c, table_class(space, c)));
         const size_t first = b->enc.swork.size();
         add_works(it, im, it.image, list, inputs[n].length, it.out, true);
         for (int c = 0; c < im.ncomp; c++) {
             const ScanWork &w = b->enc.swork[first + size_t(c)];
             TrellisWork tw;
             memset(&tw, 0, sizeof tw);
-            tw.image = it.image; tw.comp = c;
+            tw.image = it.image; tw.comp = c; tw.dc_cls = uint32_t(table_class(space, c));
             tw.table_ac = w.table_base + (progressive ? 0u : 1u);
             tw.table_dc = progressive ? -1 : int32_t(w.table_base);
             tw.nunits = w.nunits; tw.unit_base = b->tr.t_units;

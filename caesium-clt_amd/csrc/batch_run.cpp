@@ -193,7 +193,7 @@ struct Run {
         launch_idct_plane(st, b->d_imgs.p, b->pix.d_pwork.p, nw, b->max_tiles, b->d_quants.p, b->d_coef.p, b->pix.d_planes.p);
         MARK(KS_IDCT_PLANE);
         launch_resize(st, b->d_imgs.p, b->pix.d_rwork.p, int(b->pix.rwork.size()), b->pix.d_rtaps.p, b->pix.d_rweights.p, b->pix.d_planes.p, b->pix.d_rgb.p, b->pix.d_rtmp.p,
-                      b->pix.max_src_px, b->pix.max_tmp, b->pix.max_dst, b->pix.max_row_in, b->pix.max_out_w, b->pix.max_nh, !(b->webp || b->rgb_out), b->pix.any_layout_rgb);
+                      b->pix.max_src_px, b->pix.max_tmp, b->pix.max_dst, b->pix.max_row_in, b->pix.max_out_w, b->pix.max_nh, !(b->webp || b->rgb_out), b->pix.any_layout_rgb, b->pix.any_space_rgb);
         MARK(KS_RESIZE);
         return 0;
     }

@@ -176,6 +176,7 @@ int parse_jpeg(const uint8_t *d, size_t n, JpegInfo &j, std::string &msg) {
         default:
             if ((m >= 0xE0 && m <= 0xEF) || m == 0xFE) {
                 if (m == 0xEE && sl >= 12 && !memcmp(s, "Adobe", 5)) j.adobe_transform = s[11];
+                if (m == 0xE0 && sl >= 14 && !memcmp(s, "JFIF\0", 5)) j.saw_jfif = true;
                 j.meta.insert(j.meta.end(), d + i, d + i + 2 + L);
             }
         }
@@ -187,7 +188,19 @@ int parse_jpeg(const uint8_t *d, size_t n, JpegInfo &j, std::string &msg) {
         if (!j.qt_present[j.comp[c].tq]) BAD(CS_ERR_BAD_JPEG, "missing quantisation table");
     for (int c = 0; c < j.ncomp; c++)   // no scan found the slot filled: the file's last word on it
         if (!j.comp[c].qt_latched) memcpy(j.comp[c].qt, j.qt[j.comp[c].tq], sizeof j.comp[c].qt);
+    j.space = source_space(j);
     return 0;
+}
+
+int source_space(const JpegInfo &j) {
+    if (j.ncomp == 1) return CSH_CS_GREY;
+    if (j.ncomp == 3) {
+        if (j.saw_jfif) return CSH_CS_YCC;   // JFIF implies YCbCr, whatever an Adobe segment says
+        if (j.adobe_transform >= 0) return j.adobe_transform == 0 ? CSH_CS_RGB : CSH_CS_YCC;
+        return (j.comp[0].id == 'R' && j.comp[1].id == 'G' && j.comp[2].id == 'B') ? CSH_CS_RGB : CSH_CS_YCC;
+    }
+    if (j.ncomp == 4) return (j.adobe_transform < 0 || j.adobe_transform == 0) ? CSH_CS_CMYK : CSH_CS_YCCK;
+    return CSH_CS_YCC;   // (two components: refused by the planner)
 }
 
 // mozjpeg base table index 3 (natural order); j0.JPG's DQT equals this at libjpeg scale 98
@@ -208,11 +221,16 @@ void quality_table(int q, uint16_t out[64]) {
     }
 }
 
-std::vector<OutScan> output_script(int ncomp, bool progressive) {
+std::vector<OutScan> output_script(int ncomp, bool progressive, bool ycc) {
     std::vector<OutScan> v;
-    auto all = [&](int ss, int se, int ah, int al) { OutScan s{ncomp, {0, 1, 2}, ss, se, ah, al}; v.push_back(s); };
-    auto one = [&](int c, int ss, int se, int ah, int al) { OutScan s{1, {c, 0, 0}, ss, se, ah, al}; v.push_back(s); };
+    auto all = [&](int ss, int se, int ah, int al) { OutScan s{ncomp, {0, 1, 2, 3}, ss, se, ah, al}; v.push_back(s); };
+    auto one = [&](int c, int ss, int se, int ah, int al) { OutScan s{1, {c, 0, 0, 0}, ss, se, ah, al}; v.push_back(s); };
+    auto each = [&](int ss, int se, int ah, int al) { for (int c = 0; c < ncomp; c++) one(c, ss, se, ah, al); };
     if (!progressive) { all(0, 63, 0, 0); return v; }
+    if (ncomp != 1 && !(ncomp == 3 && ycc)) {   // jpeg_simple_progression's all-purpose script
+        all(0, 0, 0, 1); each(1, 5, 0, 2); each(6, 63, 0, 2); each(1, 63, 2, 1); all(0, 0, 1, 0); each(1, 63, 1, 0);
+        return v;
+    }
     if (ncomp == 3) {
         all(0, 0, 0, 1); one(0, 1, 5, 0, 2); one(2, 1, 63, 0, 1); one(1, 1, 63, 0, 1); one(0, 6, 63, 0, 2);
         one(0, 1, 63, 2, 1); all(0, 0, 1, 0); one(2, 1, 63, 1, 0); one(1, 1, 63, 1, 0); one(0, 1, 63, 1, 0);
@@ -228,7 +246,11 @@ std::vector<uint8_t> build_frame_header(const JpegInfo &g, bool progressive, con
     std::vector<uint8_t> b;
     b.push_back(0xFF); b.push_back(0xD8);
     static const uint8_t jfif[] = {0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
-    b.insert(b.end(), jfif, jfif + sizeof jfif);
+    if (g.write_jfif) b.insert(b.end(), jfif, jfif + sizeof jfif);
+    if (g.write_adobe >= 0) {   // libjpeg emit_adobe_app14: version 100, flags0 0, flags1 0, the transform
+        const uint8_t adobe[] = {0xFF, 0xEE, 0, 14, 'A', 'd', 'o', 'b', 'e', 0, 100, 0, 0, 0, 0, uint8_t(g.write_adobe)};
+        b.insert(b.end(), adobe, adobe + sizeof adobe);
+    }
     if (meta) b.insert(b.end(), meta->begin(), meta->end());
     int ids[4], ntab = 0, prec[4], len = 2;
     bool any16 = false;

@@ -9,6 +9,8 @@
 #include <string>
 #include <vector>
 
+#include "types.h"
+
 namespace csh {
 
 struct HuffSpec {
@@ -47,8 +49,18 @@ struct JpegInfo {
     bool qt_present[4] = {false, false, false, false};
     std::vector<JScan> scans;
     std::vector<uint8_t> meta;  // APPn / COM segments, raw, file order
-    int adobe_transform = -1;
+    int adobe_transform = -1;   // transform byte of the Adobe APP14 segment, -1: the file has none
+    bool saw_jfif = false;
+    int space = CSH_CS_YCC;     // CSH_CS_* (types.h): a parsed file's colour space (source_space), an output frame's
+    // an output frame (build_frame_header): the JFIF segment is written; an Adobe APP14 segment with this transform is (-1: none)
+    bool write_jfif = true;
+    int write_adobe = -1;
 };
+
+// libjpeg's default_decompress_parms: the colour space of a parsed file, from its component count, JFIF / Adobe segments and component ids
+int source_space(const JpegInfo &j);
+// libjpeg's jpeg_set_colorspace: the quantisation / Huffman table number of component c of a frame in `space`
+inline int table_class(int space, int c) { return space == CSH_CS_YCC ? (c ? 1 : 0) : (space == CSH_CS_YCCK ? (c == 1 || c == 2) : 0); }
 
 extern const uint8_t kZigZag[64];  // zig-zag index -> natural index
 
@@ -61,13 +73,14 @@ void jpeg_geometry(JpegInfo &j);
 void quality_table(int quality, uint16_t out[64]);
 
 struct OutScan {
-    int ncomp; int comp[3];
+    int ncomp; int comp[4];
     int Ss, Se, Ah, Al;
 };
-// progressive: libjpeg jpeg_simple_progression script; sequential: one interleaved scan
-std::vector<OutScan> output_script(int ncomp, bool progressive);
+// progressive: libjpeg jpeg_simple_progression script -- the one for YCbCr when ncomp == 3 and ycc, the all-purpose one (2 + 4 ncomp scans)
+// otherwise; sequential: one interleaved scan
+std::vector<OutScan> output_script(int ncomp, bool progressive, bool ycc = true);
 
-// header bytes that precede the first scan: SOI, JFIF APP0, [metadata], DQT (merged, mozjpeg style), SOFn
+// header bytes that precede the first scan: SOI, [JFIF APP0], [Adobe APP14], [metadata], DQT (merged, mozjpeg style), SOFn
 // (tables: g.qt[tq] of every table id the components refer to, in order of first use)
 std::vector<uint8_t> build_frame_header(const JpegInfo &g, bool progressive, const std::vector<uint8_t> *meta);
 }  // namespace csh

@@ -147,7 +147,7 @@ __global__ void k_decode_seq(const uint8_t *bits, ImgDesc *imgs, const DecScan *
     if (need_seq[i] == 0 || need_seq[i] == 4) return;  // the parallel decoder / the progressive wave decoder handled this image
     const ImgDesc &im = imgs[i];
     if (need_seq[i] >= 2)          // the parallel decoder gave up half-way (2: labels unresolved, 3: scan ended short): start from clean tiles
-        for (int c = 0; c < im.ncomp; c++) {
+        for (int c = 0; c < im.ncomp_in; c++) {
             int16_t *p = coef + size_t(im.in[c].tile_base) * CSH_TILE_I16;
             for (size_t n = 0; n < size_t(im.in[c].ntiles) * CSH_TILE_I16; n++) p[n] = 0;
         }
@@ -156,7 +156,7 @@ __global__ void k_decode_seq(const uint8_t *bits, ImgDesc *imgs, const DecScan *
         const DevHuffSet &hs = huffs[sc.huff_set];
         BitReader br;
         br.p = bits + sc.bits_off; br.end = br.p + sc.bits_len; br.acc = 0; br.nbits = 0; br.marker = 0; br.real = 0; br.insufficient = 0;
-        int pred[CSH_MAX_COMPS] = {0, 0, 0};
+        int pred[CSH_MAX_COMPS] = {0, 0, 0, 0};
         int eobrun = 0;
         int ri = sc.restart_interval, todo = ri;
         bool prog = im.progressive_in != 0;
@@ -165,14 +165,14 @@ __global__ void k_decode_seq(const uint8_t *bits, ImgDesc *imgs, const DecScan *
             const DevHuff &dct = hs.dc[sc.td[0] & 3], &act = hs.ac[sc.ta[0] & 3];
             for (int by = 0; by < g.real_bh; by++)
                 for (int bx = 0; bx < g.real_bw; bx++) {
-                    if (ri) { if (todo == 0) { restart(br); pred[0] = pred[1] = pred[2] = 0; eobrun = 0; todo = ri; } todo--; }
+                    if (ri) { if (todo == 0) { restart(br); pred[0] = pred[1] = pred[2] = pred[3] = 0; eobrun = 0; todo = ri; } todo--; }
                     if (br.insufficient) continue;
                     decode_block(br, sc, prog, dct, act, pred[0], eobrun, block_ref(coef, g, by, bx));
                 }
         } else {
             for (int my = 0; my < im.mcus_y; my++)
                 for (int mx = 0; mx < im.mcus_x; mx++) {
-                    if (ri) { if (todo == 0) { restart(br); pred[0] = pred[1] = pred[2] = 0; eobrun = 0; todo = ri; } todo--; }
+                    if (ri) { if (todo == 0) { restart(br); pred[0] = pred[1] = pred[2] = pred[3] = 0; eobrun = 0; todo = ri; } todo--; }
                     if (br.insufficient) continue;
                     for (int c = 0; c < sc.ncomp; c++) {
                         const CompGeom &g = im.in[sc.comp[c]];

@@ -167,7 +167,7 @@ struct ScanCtx {
 __device__ static void scan_dc_first(const ScanCtx &x, WaveReader &rd) {
     const DecScan &sc = *x.sc;
     const ImgDesc &im = *x.im;
-    int pred[CSH_MAX_COMPS] = {0, 0, 0};
+    int pred[CSH_MAX_COMPS] = {0, 0, 0, 0};
     auto one = [&](int ci, int by, int bx) {
         const CompGeom &g = im.in[sc.comp[ci]];
         uint32_t raw;

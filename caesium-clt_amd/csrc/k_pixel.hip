@@ -960,7 +960,7 @@ __global__ void __launch_bounds__(256) k_plane_fdct(const ImgDesc *__restrict__ 
     CSH_SHARED int16_t s_dr[64][256];   // deringing: a column per lane; then the wave's columns carry its retained-DCT blocks to whole-line stores (raw_copy_out); then the list's entries (nzf_phase)
     CSH_NZF_STATE;
     const PlaneWork w = work[blockIdx.y];
-    if (w.mode == 0 || w.mode == 10) return;
+    if (w.mode == 0 || w.mode == 10 || w.mode == CSH_MODE_DECODE) return;
     const ImgDesc &im = imgs[w.image];
     const CompGeom go = im.out[w.comp];
     int tile = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -1141,6 +1141,7 @@ __global__ void __launch_bounds__(256) k_resample_fdct_420(const ImgDesc *__rest
 __global__ void __launch_bounds__(256) k_requant(const ImgDesc *__restrict__ imgs, const PlaneWork *__restrict__ work, const DevQuant *__restrict__ quant, const int16_t *__restrict__ dct_raw, uint32_t raw_tile0,
                                                   int16_t *__restrict__ coef_out) {
     const PlaneWork w = work[blockIdx.y];
+    if (w.mode == CSH_MODE_DECODE) return;
     const ImgDesc &im = imgs[w.image];
     const CompGeom go = im.out[w.comp];
     int tile = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);

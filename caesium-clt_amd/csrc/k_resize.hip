@@ -1,6 +1,7 @@
 // k_resize.hip -- the resize branch of libcaesium's JPEG path (width/height set: reference parameter mapping
 // /root/reference/src/compressor.rs:503-536; engine: image 0.25.9 `resize_exact(.., Lanczos3)`, SURVEY.md 8a row R1 + J4).
 //   k_planes_to_rgb   decoded component planes -> interleaved RGB (jdsample fancy upsample + jdcolor, both libjpeg integer)
+//   k_planes_to_rgb_space   the same for RGB, CMYK and YCCK sources
 //   k_lanczos_v / _h  image-rs's separable resample: vertical pass to an f32 image, horizontal pass back to u8.
 //                     Weights (sinc(x)sinc(x/3), normalised, all f32) are computed on the HOST with the same libm calls the
 //                     oracle uses; the kernels only multiply and add -- with __fmul_rn/__fadd_rn so nothing is contracted
@@ -83,6 +84,83 @@ __global__ void __launch_bounds__(256) k_planes_to_rgb_any(const ImgDesc *imgs, 
     o[0] = uint8_t(r < 0 ? 0 : r > 255 ? 255 : r);
     o[1] = uint8_t(g < 0 ? 0 : g > 255 ? 255 : g);
     o[2] = uint8_t(b < 0 ? 0 : b > 255 ? 255 : b);
+}
+
+// A source in another colour space (ResizeWork.in_kind CSH_RZ_SPACE): R, G, B planes; C, M, Y, K planes; Y, Cb, Cr, K planes.  Launched only for
+// batches that hold such an image.
+//   RGB    the planes as they are
+//   YCCK   libjpeg's ycck_cmyk_convert first (jdcolor.c: C, M, Y = 255 - the R, G, B of ycc_rgb_convert, K as it is), then as CMYK
+//   CMYK   the samples are taken as stored inverted (255 = no ink, Adobe's convention), with or without an Adobe segment in the file -- as Pillow
+//          takes them: R = round(c k / 255), likewise G and B.  255 is odd, so c k / 255 is never half-way and this is Pillow's convert("RGB")
+// A lane takes SIXTEEN consecutive pixels of the image (in raster order, across a row end if need be): its 48 bytes of RGB start on a 16-byte
+// boundary of the pool and leave as three 16-byte stores; of a component at full resolution it reads the sixteen samples with one 16-byte
+// load when they lie in one row, and sample by sample through csh_upsample_at otherwise (a subsampled component, a row end, the image's end).
+struct Px16 { uint64_t lo, hi; };   // sixteen samples, pixel j in byte j of lo (j < 8) or byte j - 8 of hi
+__device__ __forceinline__ static int px_at(const Px16 &p, int j) { return int(((j < 8 ? p.lo : p.hi) >> (8 * (j & 7))) & 255u); }
+__device__ __forceinline__ static Px16 load_px16(const uint8_t *plane, const CompGeom &g, UpDesc u, int W, int y, int x, int n) {
+    Px16 r;
+    const int pitch = g.real_bw * 8;
+    if (u.cls == CSH_UP_COPY && n == 16 && x + 16 <= W) {   // (W <= comp_w <= pitch: the sixteen bytes lie inside the row)
+        __builtin_memcpy(&r, plane + size_t(y) * pitch + x, 16);
+        return r;
+    }
+    r.lo = r.hi = 0;
+#pragma unroll 1
+    for (int j = 0; j < n; j++) {   // (rolled: the fancy upsampling of sixteen samples unrolled costs more registers than the kernel's other paths together)
+        const uint64_t v = uint64_t(csh_upsample_at(plane, pitch, g.comp_w, g.comp_h, u, y, x)) << (8 * (j & 7));
+        if (j < 8) r.lo |= v; else r.hi |= v;
+        if (++x == W) { x = 0; y++; }
+    }
+    return r;
+}
+__device__ __forceinline__ static int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+__device__ __forceinline__ static uint32_t mul_div255(int a, int b) { const uint32_t t = uint32_t(a * b) + 128u; return (t + (t >> 8)) >> 8; }   // round(a b / 255), exact for a, b in 0..255
+__global__ void __launch_bounds__(256) k_planes_to_rgb_space(const ImgDesc *imgs, const ResizeWork *work, const uint8_t *planes, uint8_t *rgb) {
+    const ResizeWork w = work[blockIdx.y];
+    if (w.in_kind != CSH_RZ_SPACE) return;
+    const ImgDesc &im = imgs[w.image];
+    const int W = im.width, npx = W * im.height;
+    const int i0 = (blockIdx.x * blockDim.x + threadIdx.x) * 16;
+    if (i0 >= npx) return;
+    const int n = npx - i0 < 16 ? npx - i0 : 16;
+    const int y = i0 / W, x = i0 - y * W;
+    Px16 s[4];
+    CSH_UNROLL
+    for (int c = 0; c < 4; c++) {
+        if (c < im.ncomp_in) s[c] = load_px16(planes + im.plane_off[c], im.in[c], w.up[c], W, y, x, n);
+        else s[c].lo = s[c].hi = ~0ull;
+    }
+    uint32_t out[12];
+    CSH_UNROLL
+    for (int q = 0; q < 12; q++) out[q] = 0u;
+    CSH_UNROLL
+    for (int j = 0; j < 16; j++) {
+        int a = px_at(s[0], j), b = px_at(s[1], j), c = px_at(s[2], j), k = px_at(s[3], j);
+        if (w.space == CSH_CS_YCCK) {   // jdcolor.c ycck_cmyk_convert (SCALEBITS 16, as k_planes_to_rgb)
+            const int cb = b - 128, cr = c - 128;
+            const int r = clamp255(a + ((91881 * cr + 32768) >> 16));
+            const int g = clamp255(a + ((-22554 * cb + (-46802 * cr + 32768)) >> 16));
+            const int bl = clamp255(a + ((116130 * cb + 32768) >> 16));
+            a = 255 - r; b = 255 - g; c = 255 - bl;
+        }
+        if (w.space != CSH_CS_RGB) {
+            a = int(mul_div255(a, k)); b = int(mul_div255(b, k)); c = int(mul_div255(c, k));
+        }
+        out[(3 * j) >> 2] |= uint32_t(a) << (8 * ((3 * j) & 3));
+        out[(3 * j + 1) >> 2] |= uint32_t(b) << (8 * ((3 * j + 1) & 3));
+        out[(3 * j + 2) >> 2] |= uint32_t(c) << (8 * ((3 * j + 2) & 3));
+    }
+    uint8_t *o = rgb + w.rgb_src_off + size_t(i0) * 3;   // rgb_src_off is a multiple of 64, i0 of 16
+    if (n == 16) {
+        CSH_UNROLL
+        for (int q = 0; q < 3; q++) {
+            uint4 v; v.x = out[4 * q]; v.y = out[4 * q + 1]; v.z = out[4 * q + 2]; v.w = out[4 * q + 3];
+            *reinterpret_cast<uint4 *>(o + 16 * q) = v;
+        }
+    } else {
+        CSH_UNROLL
+        for (int j = 0; j < 48; j++) if (j < 3 * n) o[j] = uint8_t(out[j >> 2] >> (8 * (j & 3)));
+    }
 }
 
 // vertical pass: tmp[oy][x][c] = sum_i src[left+i][x][c] * w[i]      (f32, no clamp).  A workgroup is a piece of ONE output row, so the
@@ -239,11 +317,12 @@ __global__ void __launch_bounds__(256) k_rgb_to_planes(const ImgDesc *imgs, cons
 
 void launch_resize(hipStream_t st, const ImgDesc *imgs, const ResizeWork *work, int nwork, const ResizeTap *taps, const float *weights,
                    uint8_t *planes, uint8_t *rgb, float *tmp, uint32_t max_src_px, uint64_t max_tmp, uint64_t max_dst, uint32_t max_row_in, uint32_t max_out_w, uint32_t max_nh, bool to_planes,
-                   bool any_layout) {
+                   bool any_layout, bool any_space) {
     (void)max_tmp;
     if (!nwork) return;
     CSH_LAUNCH(k_planes_to_rgb, dim3((max_src_px + 255) / 256, nwork), dim3(256), st, imgs, work, planes, rgb);
     if (any_layout) CSH_LAUNCH(k_planes_to_rgb_any, dim3((max_src_px + 255) / 256, nwork), dim3(256), st, imgs, work, planes, rgb);
+    if (any_space) CSH_LAUNCH(k_planes_to_rgb_space, dim3(((max_src_px + 15) / 16 + 255) / 256, nwork), dim3(256), st, imgs, work, planes, rgb);
     if (resize_is_fused(max_row_in)) {   // (source and result lie in different stretches of the RGB pool: rgb_src_off / rgb_dst_off)
         if (max_row_in <= uint32_t(CSH_RZ_CAP_S)) CSH_LAUNCH_PHASED(k_lanczos_fused<CSH_RZ_CAP_S>, 2, dim3(max_nh, nwork), dim3(256), st, imgs, work, taps, weights, rgb, rgb);
         else CSH_LAUNCH_PHASED(k_lanczos_fused<CSH_RZ_CAP_L>, 2, dim3(max_nh, nwork), dim3(256), st, imgs, work, taps, weights, rgb, rgb);

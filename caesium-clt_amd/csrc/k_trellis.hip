@@ -435,7 +435,7 @@ __global__ void __launch_bounds__(64) k_trellis_dc(TrellisCtx c) {
     // out where they are needed: measured, no faster)
     CSH_SHARED float s_costs[64][13];   // (a column per lane: the lanes of a wave belong to different components now)
     float *s_cost = s_costs[threadIdx.x & 63u];
-    for (int i = 0; i < 12; i++) s_cost[i] = float(i + int(w.table_dc < 0 ? kStdDcLen[w.comp ? 1 : 0][i] : c.tables[w.table_dc].size[i]));
+    for (int i = 0; i < 12; i++) s_cost[i] = float(i + int(w.table_dc < 0 ? kStdDcLen[w.dc_cls ? 1 : 0][i] : c.tables[w.table_dc].size[i]));
     s_cost[12] = __builtin_inff();   // a difference no two real levels make (they stay within 11 bits): only the closed form's pairs with a level past ncand, infinite anyway, read it
     const int q = Q.div[0];
     const uint32_t qmul = Q.mul[0], qsh = Q.sh[0];

@@ -114,7 +114,7 @@ void launch_fix_dummy(hipStream_t st, const ImgDesc *imgs, int nimg, int max_blo
 bool resize_is_fused(uint32_t max_row_in);   // both Lanczos passes in one kernel, no f32 intermediate image (the batch's widest source row fits LDS)
 void launch_resize(hipStream_t st, const ImgDesc *imgs, const ResizeWork *work, int nwork, const ResizeTap *taps, const float *weights,
                    uint8_t *planes, uint8_t *rgb, float *tmp, uint32_t max_src_px, uint64_t max_tmp, uint64_t max_dst, uint32_t max_row_in, uint32_t max_out_w, uint32_t max_nh, bool to_planes,
-                   bool any_layout = false);   // any_layout: the batch has ResizeWork items of CSH_RZ_ANY (k_planes_to_rgb_any)
+                   bool any_layout = false, bool any_space = false);   // any_layout / any_space: the batch has ResizeWork items of CSH_RZ_ANY (k_planes_to_rgb_any) / of CSH_RZ_SPACE (k_planes_to_rgb_space)
 
 // ---- phases 2-5: entropy encode (k_entropy.hip)
 // tokens -> runs -> tables -> chunk sizes -> (scan) -> pack.  A token is one u32 (k_entropy.hip); the tokens of one (scan, 256-unit

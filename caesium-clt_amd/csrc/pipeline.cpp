@@ -277,7 +277,7 @@ static int batch_run(csh_batch *b, csh_timing *t, bool requant_only) {
         for (int i = 0; i < b->nimg; i++) { t->out_bytes += b->out.h_img_size[i]; t->pixels += uint64_t(b->imgs[i].width) * b->imgs[i].height; }
         t->in_bytes = b->dec.bits_pool.size();
         uint64_t in_tiles = 0;
-        for (const ImgDesc &im : b->imgs) for (int c = 0; c < im.ncomp; c++) in_tiles += im.in[c].ntiles;
+        for (const ImgDesc &im : b->imgs) for (int c = 0; c < im.ncomp_in; c++) in_tiles += im.in[c].ntiles;
         t->coef_bytes = in_tiles * CSH_TILE_I16 * 2;
     }
     b->out.ran = true;
@@ -348,7 +348,7 @@ extern "C" int csh_batch_fetch(csh_batch *b, CByteArray *outputs, CCSResult *res
 extern "C" int csh_batch_geometry(csh_batch *b, size_t image, int comp, int which, int *bw, int *bh, int *real_bw, int *real_bh) {
     if (image >= b->items.size() || b->items[image].image < 0) { csh_set_error("image not on the device"); return -1; }
     const ImgDesc &im = b->imgs[b->items[image].image];
-    if (comp < 0 || comp >= im.ncomp) { csh_set_error("bad component"); return -1; }
+    if (comp < 0 || comp >= (which ? im.ncomp : im.ncomp_in)) { csh_set_error("bad component"); return -1; }
     const CompGeom &g = which ? im.out[comp] : im.in[comp];
     *bw = g.bw; *bh = g.bh; *real_bw = g.real_bw; *real_bh = g.real_bh;
     return 0;

@@ -54,6 +54,7 @@ int search_decide(csh_batch *b, int stage) {
     for (int i = 0; i < b->nimg; i++) {
         SearchImg &si = b->enc.simg[size_t(i)];
         const ImgDesc &im = b->imgs[size_t(i)];
+        if (si.fixed) continue;
         auto size = [&](int cand) -> uint64_t { return b->enc.h_cost[size_t(search_work(si, cand))]; };
         auto luma_split = [&](int idx) { return idx == 0 ? size(kLumaSplit0) : size(kLumaSplit0 + 2 * idx - 1) + size(kLumaSplit0 + 2 * idx); };
         auto chroma_split = [&](int idx) {
@@ -133,6 +134,7 @@ int search_lists(csh_batch *b) {
     for (int i = 0; i < b->nimg; i++) {
         const SearchImg &si = b->enc.simg[size_t(i)];
         const ImgDesc &im = b->imgs[size_t(i)];
+        if (si.fixed) continue;   // its list was written with its work items (batch_plan.cpp output_scans)
         uint32_t *list = b->enc.img_list.data() + size_t(i) * CSH_LIST_MAX;
         uint32_t m = 0;
         auto put = [&](int cand) { list[m++] = uint32_t(search_work(si, cand)); };

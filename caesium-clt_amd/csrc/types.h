@@ -25,13 +25,13 @@
 #define CSH_OCT_STRIDE 512
 #define CSH_BLK_STRIDE 8
 #endif
-#define CSH_MAX_COMPS 3
+#define CSH_MAX_COMPS 4   // Adobe CMYK / YCCK files carry four
 // per-block 64-bit planes (bit = zig-zag index), SoA per tile u64[CSH_MASK_PLANES][64]:
 // 0..2 significance |c| >= 1, 2, 4;  3, 4 = bit 0, bit 1 of |c|;  5 = sign.  Refinement scans are coded from these alone.
 #define CSH_MASK_PLANES 6
 #define CSH_MASK_TILE (CSH_MASK_PLANES * 64)
 #define CSH_MAX_SCANS 20
-#define CSH_LIST_MAX 16   // scans of one output file (the scan search ends with at most 14)
+#define CSH_LIST_MAX 18   // scans of one output file (the scan search ends with at most 14; libjpeg's all-purpose script has 2 + 4 per component)
 
 namespace csh {
 
@@ -94,7 +94,8 @@ struct RefineUnit { int chain, s, prev; };   // one scan of a refinement chain =
 struct ProgChain { int image, first, count, refine, comp; uint32_t nblocks, hist_off, pos_off; };   // chain_scans[first .. first+count) = DecScan indices
 
 struct ImgDesc {
-    int width, height, ncomp;
+    int width, height, ncomp;     // ncomp: components of the OUTPUT frame = samples per pixel of the image's RGB (resize branch)
+    int ncomp_in;                 // components of the INPUT frame: differs from ncomp where an RGB / CMYK / YCCK source is converted (k_planes_to_rgb_space)
     int mcus_x, mcus_y;           // MCU grid of the INPUT frame (entropy decode)
     int omcus_x, omcus_y;         // MCU grid of the OUTPUT frame (entropy encode)
     int progressive_in;
@@ -161,6 +162,7 @@ struct UpDesc { uint8_t cls, hx, vx, pad; };   // decoded plane -> full resoluti
 
 // work item of the pixel kernels: one component of one image
 #define CSH_MODE_ANY 11
+#define CSH_MODE_DECODE 12   // a source component the output frame has no counterpart of (K of a converted CMYK file): IDCT to its plane, nothing on the encoder side
 struct PlaneWork {
     int image, comp;
     // 0: full-res in and out (IDCT->FDCT in one lane); 10: h2v2 kept, no resize (k_resample_fdct_420); 1 + 3*in_kind + out_kind with kinds 0 full,
@@ -176,9 +178,14 @@ struct PlaneWork {
 
 // resize path work item (k_resize.hip): one image
 #define CSH_RZ_ANY (-2)
+#define CSH_RZ_SPACE (-3)
+// colour space of a source (libjpeg default_decompress_parms; jpeg_host.cpp source_space)
+enum { CSH_CS_GREY = 0, CSH_CS_YCC = 1, CSH_CS_RGB = 2, CSH_CS_CMYK = 3, CSH_CS_YCCK = 4 };
 struct ResizeWork {
     int image, in_kind;            // in_kind: how the decoded chroma planes relate to full resolution (0 full, 1 h2v2, 2 h2v1); -1 a pixel source;
-                                   // CSH_RZ_ANY: any other layout, per component from `up` (k_planes_to_rgb_any)
+                                   // CSH_RZ_ANY: any other layout, per component from `up` (k_planes_to_rgb_any);
+                                   // CSH_RZ_SPACE: an RGB / CMYK / YCCK source, per component from `up` (k_planes_to_rgb_space)
+    int space, pad;                // CSH_RZ_SPACE: CSH_CS_*
     UpDesc up[CSH_MAX_COMPS];
     int nw, nh;                    // new size
     uint64_t rgb_src_off, rgb_dst_off;  // byte offsets in the RGB pool (W*H*nc source, nw*nh*nc resized)
@@ -295,6 +302,7 @@ struct TrellisWork {
     uint32_t unit_base;      // first entry of the component in the per-block side arrays (lambda, DC back-pointers)
     uint32_t nzset;          // the component's NzSet (its level-0 list takes the chosen levels: TrellisCtx::nz_pool), 0xFFFFFFFF: none
     uint32_t ac_lists;       // 1: the component's AC levels live in that list alone (PlaneWork::ac_lists): in a run that says so (TrellisCtx::ac_lists) k_trellis_ac does not store them to the tile
+    uint32_t dc_cls;         // the component's libjpeg table number (0 luma-like, 1 chroma-like): the Annex K DC code lengths the DC trellis counts with
 };
 // what one grab of k_trellis_ac's queue hands a workgroup: chunks j .. j + n - 1 of a work item (one staging of its tables for all n)
 struct TrellisRun { uint32_t work, j, n; };

@@ -37,7 +37,7 @@ enum {
     CS_ERR_UNKNOWN_TYPE = 10200,   /* magic bytes not recognised */
     CS_ERR_UNSUPPORTED = 10201,    /* recognised, but this build has no device path for it yet */
     CS_ERR_BAD_JPEG = 20100,       /* malformed / truncated JPEG */
-    CS_ERR_JPEG_FEATURE = 20101,   /* arithmetic coding, 12-bit, CMYK, unsupported sampling ... */
+    CS_ERR_JPEG_FEATURE = 20101,   /* arithmetic coding, 12-bit, two components, unsupported sampling ... (CMYK, YCCK and RGB-colourspace files are coded) */
     CS_ERR_POOL_OVERFLOW = 20200,  /* internal device pool too small even after retry */
     CS_ERR_BAD_PNG = 30100,        /* malformed / truncated PNG (chunk walk, zlib stream, filter bytes) */
     CS_ERR_BAD_WEBP = 40100,       /* malformed / truncated WebP (RIFF chunk walk, VP8 frame header, bool-coded data running out) */
@@ -85,7 +85,7 @@ CCSResult cs_compress_in_memory(const uint8_t *in, size_t n, const CCSParameters
    are overwritten while bisecting, as the reference's &mut CSParameters is) */
 CCSResult cs_compress_to_size_in_memory(const uint8_t *in, size_t n, CCSParameters *p, size_t max_output_size,
                                         bool return_smallest, CByteArray *out);
-/* replaces caesium::convert_in_memory (compressor.rs:289,300).  Built: JPEG -> WebP and PNG -> WebP (lossy, or lossless with webp_lossless; a PNG's transparency is kept: an ALPH chunk / ARGB), JPEG -> PNG (png_optimize: lossless trials, else the quantiser), PNG -> JPEG (alpha dropped), WebP -> JPEG / PNG; every other pair answers CS_ERR_UNSUPPORTED (or CS_ERR_SAME_FORMAT) */
+/* replaces caesium::convert_in_memory (compressor.rs:289,300).  Built: JPEG -> WebP and PNG -> WebP (lossy, or lossless with webp_lossless; a PNG's transparency is kept: an ALPH chunk / ARGB), JPEG -> PNG (png_optimize: lossless trials, else the quantiser; a CMYK, YCCK or RGB-colourspace JPEG is converted to RGB first, here and toward WebP), PNG -> JPEG (alpha dropped), WebP -> JPEG / PNG; every other pair answers CS_ERR_UNSUPPORTED (or CS_ERR_SAME_FORMAT) */
 CCSResult cs_convert_in_memory(const uint8_t *in, size_t n, const CCSParameters *p, uint32_t format, CByteArray *out);
 /* the batch form of it: results[i] / outputs[i] correspond to inputs[i] */
 int cs_batch_convert(const CByteArray *inputs, size_t count, const CCSParameters *p, uint32_t format, int device, CByteArray *outputs, CCSResult *results);
