@@ -107,6 +107,8 @@ struct EncodePlan {
     uint32_t nslots = 0, nlist_slots = 0, ntok_slots = 0;
     uint32_t nref_slots = 0;              // those of the token-coded slots whose tokens k_list_refine makes (refinement scans coded from their list)
     uint32_t last_run_refine = 0;         // refinement work items the last run coded from lists (csh_timing.n_list_refine)
+    uint32_t last_run_ref_packed = 0;     // ... and those of them it packed from the lists, without tokens (csh_timing.n_ref_packed)
+    bool ref_pack = true;                 // PlanSwitches::ref_pack
     // k_list_stats, k_list_pack and k_list_refine take one wave per run of up to list_run consecutive chunks of a work item: the runs are counted beside the slots
     uint32_t list_run = CSH_LIST_RUN;     // PlanSwitches::list_run
     uint32_t nlist_runs = 0, nref_runs = 0;
@@ -180,7 +182,7 @@ struct EncodePlan {
     DevBuf<uint64_t> d_corr, d_symbits, d_eobbits, d_tok_off, d_chunk_off, d_scan_raw_off;
     DevBuf<uint32_t> d_tok_cursor;
     DevBuf<TokRegion> d_regions;
-    DevBuf<uint16_t> d_eobrun, d_slot_hist;
+    DevBuf<uint16_t> d_eobrun, d_slot_hist, d_lastn;
     DevBuf<uint32_t> d_img_list, d_img_nlist, d_scan_cost, d_slot_raw, d_slot_eobh, d_long_runs, d_long_cnt, d_tokens, d_chunk_ntok, d_chunk_bits, d_raw, d_scan_pad, d_chunk_ff, d_hdr_off;
     DevBuf<DevEncTable> d_tables;
     DevBuf<NzList> d_nzlists;
@@ -314,6 +316,7 @@ struct PlanSwitches {
     bool fused_420 = true;      // CSH_NO_FUSED_420 unset
     bool nz_fused = true;       // CSH_NZ_FUSED != "0": the forward-DCT kernels build the level-0 coefficient lists
     bool ref_list = true;       // CSH_REF_LIST != "0": the AC refinement scans are coded from the coefficient lists (k_list_refine), not from the tiles (k_tokens' kind-0 chunks)
+    bool ref_pack = true;       // CSH_REF_PACK != "0" (and ref_list): those scans are packed from the lists too (k_list_refine_pack): no token, no token region, not in tok_slots
     uint32_t list_run = CSH_LIST_RUN;   // CSH_LIST_RUN, clamped to 1..32: chunks per wave of k_list_stats, k_list_pack and k_list_refine (1: one wave per chunk)
     bool ac_runs_slot = false;  // CSH_AC_RUNS == "slot": k_ac_runs takes one wave per slot, as before it took one per 16 slots (k_ac_runs_words)
     bool ac_tiles = false;      // CSH_AC_TILES == "1": every component's AC levels are stored to its tiles, as before they lived in the lists

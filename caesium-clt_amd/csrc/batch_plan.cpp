@@ -246,6 +246,7 @@ PlanSwitches PlanSwitches::read() {
     s.nz_fused = !is("CSH_NZ_FUSED", "0");
     s.ac_tiles = is("CSH_AC_TILES", "1");
     s.ref_list = is("CSH_REF_LIST", "1") || (s.ref_list && !is("CSH_REF_LIST", "0"));   // "1" / "0" name the path, anything else leaves the default
+    s.ref_pack = s.ref_list && (is("CSH_REF_PACK", "1") || (s.ref_pack && !is("CSH_REF_PACK", "0")));   // the same; CSH_REF_LIST=0 switches it off by itself
     const char *pp = getenv("CSH_PROG_PAR");
     s.prog_par = pp && !strcmp(pp, "0") ? 0 : (pp && !strcmp(pp, "1") ? 1 : -1);
     s.fused_420 = !getenv("CSH_NO_FUSED_420");
@@ -277,6 +278,7 @@ void BatchPlanner::begin() {
     b->progressive = progressive;
     b->enc.list_run = sw.list_run;
     b->enc.ac_runs_slot = sw.ac_runs_slot;
+    b->enc.ref_pack = sw.ref_pack;
 
     add_script(b->enc.script, 3, true, CSH_CS_YCC);    // entries 0..9
     add_script(b->enc.script, 1, true, CSH_CS_GREY);   // entries 10..15
@@ -404,7 +406,8 @@ void BatchPlanner::add_works(Item &it, ImgDesc &im, int img_index, const std::ve
         w.image = img_index; w.scan = sidx;
         w.out_off = 0xFFFFFFFFu;   // not part of a file until k_layout says so (a conditional stage of the scan search may never run)
         // progressive AC scans are coded from the component's compacted list at their Al: first-pass scans entirely (k_list_stats, k_list_pack), refinement
-        // scans through tokens k_list_refine makes from it (CSH_REF_LIST=0: through k_tokens' kind-0 chunks, from the tiles); everything else from tokens
+        // scans by k_list_refine and k_list_refine_pack (CSH_REF_PACK=0: through tokens k_list_refine makes from it; CSH_REF_LIST=0: through k_tokens' kind-0 chunks,
+        // from the tiles); everything else from tokens
         const bool from_list = e.Ss > 0 && !e.sequential && e.Ah == 0;
         const bool ref_list = sw.ref_list && e.Ss > 0 && !e.sequential && e.Ah != 0;
         w.list = 0xFFFFFFFFu; w.rs_base = 0xFFFFFFFFu; w.lr_base = 0xFFFFFFFFu; w.rr_base = 0xFFFFFFFFu;
@@ -431,8 +434,12 @@ void BatchPlanner::add_works(Item &it, ImgDesc &im, int img_index, const std::ve
             const uint32_t nch = (w.nunits + 255) / 256;
             w.first_chunk = b->enc.nslots; b->enc.nslots += nch;
             w.hist_row0 = b->enc.hist_rows; b->enc.hist_rows += nch * uint32_t(e.ntables);
-            uint32_t &cursor = (from_list && w.list != 0xFFFFFFFFu) ? b->enc.nlist_slots : b->enc.ntok_slots;
-            w.ls_base = cursor; cursor += nch;
+            // a refinement scan packed from its list (CSH_REF_PACK) is in neither slot list: k_list_refine_pack takes it by its runs
+            if (ref_list && sw.ref_pack && w.list != 0xFFFFFFFFu) w.ls_base = 0xFFFFFFFFu;
+            else {
+                uint32_t &cursor = (from_list && w.list != 0xFFFFFFFFu) ? b->enc.nlist_slots : b->enc.ntok_slots;
+                w.ls_base = cursor; cursor += nch;
+            }
             if (ref_list && w.list != 0xFFFFFFFFu) { w.rs_base = b->enc.nref_slots; b->enc.nref_slots += nch; }
             // ... and its runs of up to list_run chunks, one wave of the list kernels each
             const uint32_t nruns = (nch + b->enc.list_run - 1) / b->enc.list_run;
@@ -475,6 +482,7 @@ void BatchPlanner::add_works(Item &it, ImgDesc &im, int img_index, const std::ve
         const uint64_t blocks_all = blocks_of(im);
         const uint64_t scripts = b->enc.search ? uint64_t(nac + 1) / 2 : 1;
         const uint64_t est = uint64_t(in_len) * 3 * scripts * nu / std::max<uint64_t>(1, blocks_all) + uint64_t(nu) * nac + 1024;
+        if (sw.ref_list && sw.ref_pack) continue;   // coded and packed from the lists: no plan, no token chunk, no region
         if (sw.ref_list) {   // coded from the lists: no plan, no token chunk -- the scans' slots name the component's region themselves
             for (size_t k = 0; k < list.size(); k++) {
                 const EncScan &e = b->enc.script[list[k]];
@@ -1232,7 +1240,7 @@ int BatchPlanner::upload(Laps &laps) {
         return CS_ERR_NO_DEVICE;
     if (b->d_coef.alloc(size_t(b->ntiles) * CSH_TILE_I16) || b->pix.d_planes.alloc(b->pix.plane_bytes + 64) || b->pix.d_oplanes.alloc(b->pix.oplane_bytes + 64) ||
         b->enc.d_symbits.alloc(b->enc.total_words + 1) || b->enc.d_eobbits.alloc(b->enc.total_words + 1) ||
-        b->enc.d_long_runs.alloc(2 * (b->enc.total_units / 512 + b->enc.swork.size() + 16)) || b->enc.d_long_cnt.alloc(4) || b->enc.d_tail.alloc(b->enc.total_units + 1) || b->enc.d_eobrun.alloc(b->enc.total_units + 1) || b->enc.d_corr.alloc(b->enc.total_corr + 1) ||
+        b->enc.d_long_runs.alloc(2 * (b->enc.total_units / 512 + b->enc.swork.size() + 16)) || b->enc.d_long_cnt.alloc(4) || b->enc.d_tail.alloc(b->enc.total_units + 1) || b->enc.d_eobrun.alloc(b->enc.total_units + 1) || b->enc.d_corr.alloc(b->enc.total_corr + 1) || b->enc.d_lastn.alloc((b->enc.ref_pack ? b->enc.total_corr : 0) + 1) ||
         b->enc.d_tok_off.alloc(4 * size_t(b->enc.nslots) + 4) || b->enc.d_chunk_ntok.alloc(4 * size_t(b->enc.nslots) + 4) || b->enc.d_slot_hist.alloc(size_t(b->enc.hist_rows) * 256 + 256) ||
         b->enc.d_slot_raw.alloc(size_t(b->enc.nslots) + 1) || b->enc.d_img_list.upload(b->enc.img_list, st) || b->enc.d_img_nlist.upload(b->enc.img_nlist, st) || b->enc.d_scan_cost.alloc(b->enc.swork.size() + 1) || b->enc.d_slot_eobh.alloc(16 * size_t(b->enc.nslots) + 16) || b->enc.d_chunk_bits.alloc(size_t(b->enc.nslots) + 1) || b->enc.d_chunk_off.alloc(size_t(b->enc.nslots) + 2) || b->enc.d_tok_cursor.alloc(b->enc.region_est.size() + 1) || b->enc.d_regions.upload(b->enc.regions, st) ||
         b->enc.d_tables.alloc(b->enc.ntables) || b->enc.d_scan_pad.alloc(b->enc.swork.size() + 1) ||

@@ -233,7 +233,7 @@ struct Run {
         c.imgs = b->d_imgs.p; c.script = b->enc.d_script.p; c.work = b->enc.d_swork.p; c.nwork = int(b->enc.swork.size());
         c.echunks = b->enc.d_echunks.p; c.plans = b->enc.d_plans.p; c.nechunks = uint32_t(b->enc.echunks.size()); c.slot_work = b->enc.d_slot_work.p; c.slots = b->enc.d_slots.p; c.nslots = b->enc.nslots;
         c.coef = b->d_coef.p; c.sym_bits = b->enc.d_symbits.p; c.eob_bits = b->enc.d_eobbits.p; c.tail = b->enc.d_tail.p;
-        c.eobrun = b->enc.d_eobrun.p; c.long_runs = b->enc.d_long_runs.p; c.long_cnt = b->enc.d_long_cnt.p; c.corr = b->enc.d_corr.p;
+        c.eobrun = b->enc.d_eobrun.p; c.long_runs = b->enc.d_long_runs.p; c.long_cnt = b->enc.d_long_cnt.p; c.corr = b->enc.d_corr.p; c.lastn = b->enc.d_lastn.p; c.ref_pack = b->enc.ref_pack ? 1u : 0u;
         c.tokens = b->enc.d_tokens.p; c.regions = b->enc.d_regions.p; c.tok_cursor = b->enc.d_tok_cursor.p; c.tok_off = b->enc.d_tok_off.p; c.chunk_ntok = b->enc.d_chunk_ntok.p; c.slot_hist = b->enc.d_slot_hist.p; c.slot_raw = b->enc.d_slot_raw.p; c.slot_eobh = b->enc.d_slot_eobh.p;
         c.chunk_bits = b->enc.d_chunk_bits.p; c.chunk_off = b->enc.d_chunk_off.p; c.tables = b->enc.d_tables.p;
         c.raw = b->enc.d_raw.p; c.raw_words = raw_chunks * 16; c.status = b->out.d_status.p; c.overflow = b->out.d_overflow.p;
@@ -347,7 +347,7 @@ struct Run {
         SMARK(KS_NZLIST);
         launch_list_refine(st, c);  // AC refinement scans, from the lists (timed with k_tokens, whose kind-0 chunks they were)
         for (uint32_t wi = sg.work0; sg.nrs && wi < sg.work0 + sg.nwork; wi++)
-            if (b->enc.swork[wi].rs_base != 0xFFFFFFFFu && (!gate || b->enc.work_active[wi])) b->enc.last_run_refine++;
+            if (b->enc.swork[wi].rs_base != 0xFFFFFFFFu && (!gate || b->enc.work_active[wi])) { b->enc.last_run_refine++; if (b->enc.ref_pack) b->enc.last_run_ref_packed++; }
         count_list_runs(sg, gate);
         launch_tokens(st, c);       // DC and sequential-mode scans (CSH_REF_LIST=0: the refinement scans too, from the tiles)
         SMARK(KS_TOKENS);
@@ -367,6 +367,7 @@ struct Run {
         launch_zero_edges(st, c);
         SMARK(KS_SCAN_LAYOUT);
         launch_pack(st, c);
+        launch_list_refine_pack(st, c);   // AC refinement scans, from the lists (CSH_REF_PACK; timed with k_pack, which packed their tokens)
         SMARK(KS_PACK);
         launch_list_pack(st, c);
         SMARK(KS_LIST_PACK);
@@ -455,7 +456,7 @@ struct Run {
 int run_once(csh_batch *b, csh_timing *t, bool requant_only) {
     Run r(b, t);
     b->enc.last_run_list_runs = 0;
-    b->enc.last_run_fused = 0; b->enc.last_run_refine = 0; b->enc.last_run_ac_lists = 0;
+    b->enc.last_run_fused = 0; b->enc.last_run_refine = 0; b->enc.last_run_ref_packed = 0; b->enc.last_run_ac_lists = 0;
     if (r.pools() || r.marks.start()) return -1;
     // a re-run at another quality (size targeting): from the retained DCT -- unless the batch derings: the overshoot mozjpeg's deringing allows
     // depends on the DC quantiser (jcdctmgr.c preprocess_deringing), so the forward DCT's input changes with the table and the re-run starts

@@ -1,5 +1,6 @@
 // k_aclist.hip -- progressive AC scans coded from COMPACTED COEFFICIENT LISTS: the first-pass scans (Ah = 0) entirely, the refinement scans
-// (Ah = Al + 1) up to their tokens (k_list_refine, at the end of the file; CSH_REF_LIST=0 leaves them to k_tokens).
+// (Ah = Al + 1) too (k_list_refine and k_list_refine_pack, at the end of the file; CSH_REF_PACK=0: up to their tokens, which k_pack packs; CSH_REF_LIST=0 leaves
+// them to k_tokens).
 //
 // Replaces, for those scans, the per-block sweeps of k_entropy.hip's k_tokens and the token stream between it and k_pack (mozjpeg
 // jcphuff.c encode_mcu_AC_first + jchuff.c statistics, reached from /root/reference/src/compressor.rs:305).
@@ -18,6 +19,7 @@
 // The kernels are written once for both builds (wave.h): the emulation runs the statements the device runs.
 #include "kernels.h"
 #include "wave.h"
+#include "tok_bits.h"
 
 namespace csh {
 
@@ -592,7 +594,8 @@ __global__ void __launch_bounds__(256) k_list_pack(EncCtx c) {
 //   first token of an entry, none for further ones.  The block's END entry is its EOB (unless an N sits at Se), with the H entries left.
 // Pass 1 takes everything but the tokens -- histogram, correction words, tails, flags, raw bits, the number of tokens -- and leaves per block
 // its last N and its H count in LDS; pass 2 reads the chunk again (out of the L2) and writes the tokens behind one atomic add on the region's
-// cursor.  All of a slot's tokens are its segment 0 (k_pack walks the four segments as one list).
+// cursor.  All of a slot's tokens are its segment 0 (k_pack walks the four segments as one list).  Under CSH_REF_PACK (the default) pass 2 is not run here:
+// k_list_refine_pack, below, runs its statements once the tables exist and turns the tokens into bits without storing them.
 struct RefCarry { uint32_t runH, runN, base, prevN, prevNZ; };
 __device__ __forceinline__ static uint32_t ref_isN(uint32_t e, uint32_t Ss, uint32_t Se) { const uint32_t k = e & 127u; return (k >= Ss && k <= Se && ((e >> 8) & 0x7FFFu) == 1u) ? 1u : 0u; }
 __device__ __forceinline__ static uint32_t ref_isH(uint32_t e, uint32_t Ss, uint32_t Se) { const uint32_t k = e & 127u; return (k >= Ss && k <= Se && ((e >> 8) & 0x7FFFu) >= 2u) ? 1u : 0u; }
@@ -647,6 +650,60 @@ __device__ __forceinline__ static void ref_step(const LV<uint32_t> (&e)[4], uint
         }
     }
 }
+// one step's tokens, behind ref_step<true>: per entry its ZRLs and its tokens (zq <- ZRLs | tokens << 8), the key of the block's last emitting entry in front
+// of it (curc: carried across the steps of a chunk), a wave scan of the counts, and the token words at tk[at ...] in list order -- none at `limit` or behind it.
+// lastn / nh: the chunk's blocks' last N (k << 6 | hex) and H entries, in LDS.  Returns the step's number of tokens.  Pass 2 of k_list_refine<true> stores
+// them in the token pool; k_list_refine_pack in an LDS buffer it turns into bits at once: the same words either way
+template <class TL, class TN>
+__device__ __forceinline__ static uint32_t ref_step_tokens(const LV<uint32_t> (&e)[4], const LV<uint32_t> (&hex)[4], const LV<uint32_t> (&z)[4], const LV<uint32_t> (&zp)[4], LV<uint32_t> (&zq)[4],
+                                                           uint32_t Ss, uint32_t Se, const TL *lastn, const TN *nh, uint32_t &curc, uint32_t *tk, uint32_t at, uint32_t limit) {
+    LV<uint32_t> cur[4], nt;
+    LFOR(l) {
+        uint32_t s = 0;
+        CSH_UNROLL
+        for (int q = 0; q < 4; q++) {
+            const uint32_t v = e[q][l], blk = (v >> 23) & 255u, lastk = uint32_t(lastn[blk]) >> 6, isN = ref_isN(v, Ss, Se);
+            uint32_t nz = 0, n = 0;
+            if ((isN | ref_isH(v, Ss, Se)) && (v & 127u) <= lastk) { nz = ((z[q][l] - zp[q][l]) >> 4) - ((zq[q][l] - zp[q][l]) >> 4); n = nz + isN; }
+            cur[q][l] = n ? ((blk + 1u) << 6) | hex[q][l] : 0u;
+            if ((v & CSH_NZ_END) && lastk != Se) n = 1u;
+            zq[q][l] = nz | (n << 8);
+            s += n;
+        }
+        nt[l] = s;
+    }
+    lscan_last4(cur, curc);
+    uint32_t tot;
+    const LV<uint32_t> ex = lscan(nt, tot);
+    LFOR(l) {
+        uint32_t o = at + ex[l];
+        CSH_UNROLL
+        for (int q = 0; q < 4; q++) {
+            const uint32_t v = e[q][l], blk = (v >> 23) & 255u, nz = zq[q][l] & 255u, n = zq[q][l] >> 8;
+            if (!n) continue;
+            const uint32_t cu = ref_same(cur[q][l], blk);
+            if (v & CSH_NZ_END) {
+                if (o < limit) tk[o] = TK_EOB | (blk << 3) | ((uint32_t(nh[blk]) - cu) << 16) | (cu << 22);
+                o++;
+                continue;
+            }
+            // the first token takes the correction bits since the block's last emitting entry, the others none
+            uint32_t cnt = hex[q][l] - cu, from = cu;
+            for (uint32_t t = 0; t < nz; t++) {
+                if (o < limit) tk[o] = TK_REF | (blk << 3) | (cnt << 16) | (from << 22) | (1u << 28);
+                o++; cnt = 0u; from = hex[q][l];
+            }
+            if (n > nz) {
+                if (o < limit) tk[o] = TK_REF | (blk << 3) | (((z[q][l] - zp[q][l]) & 15u) << 11) | ((v & 128u) ? 0u : (1u << 15)) | (cnt << 16) | (from << 22);
+                o++;
+            }
+        }
+    }
+    return tot;
+}
+// TOKENS = false (CSH_REF_PACK, the default): the kernel stops after pass 1 -- it also stores every block's last N (lastn[], indexed like corr[]), and
+// k_list_refine_pack below derives the events again once the tables exist; no token, no reservation, no token region
+template <bool TOKENS>
 __global__ void __launch_bounds__(256, 5) k_list_refine(EncCtx c) {   // (five waves per SIMD: what its 32 KB of LDS per workgroup allow)
     CSH_SHARED alignas(16) uint32_t s_hist[4][4][256];   // four copies, lane & 3 (k_list_stats)
     CSH_SHARED uint32_t s_lastn[4][256];     // per block: its last N, k << 6 | hex (0: no N)
@@ -661,7 +718,9 @@ __global__ void __launch_bounds__(256, 5) k_list_refine(EncCtx c) {   // (five w
     const uint32_t nrun = run_chunks(c, r);
     const uint64_t lbase = c.nzlists[r.nzlist].base;
     ListSlot nx = list_chunk(c, lbase, r.nzrec);
-    const TokRegion rg = c.regions[r.region];
+    TokRegion rg;
+    rg.base = 0; rg.cap = 0; rg.pad = 0;
+    if (TOKENS) rg = c.regions[r.region];
     uint32_t *hist = &s_hist[wv][0][0], *lastn = s_lastn[wv], *nh = s_nh[wv], *corr = &s_corr[wv][0][0];
     LFOR(l) {   // (a chunk's flush leaves it at zero for the next)
         uint4 zero; zero.x = zero.y = zero.z = zero.w = 0u;
@@ -721,6 +780,7 @@ __global__ void __launch_bounds__(256, 5) k_list_refine(EncCtx c) {   // (five w
                     if (ls.n && (ln >> 6) != Se) ntok[l] += 1u;   // (no entries: the list had no room, the run is repeated)
                     c.tail[unit0 + i] = uint8_t(nh[i] - (ln & 63u));   // the H entries behind the last N; all of them if there is no N
                     c.corr[corr0 + i] = (uint64_t(corr[2u * i]) << 32) | corr[2u * i + 1u];
+                    if (!TOKENS) c.lastn[corr0 + i] = uint16_t(ln);   // k << 6 | hex, k <= 63: the block's H entries are tail + (lastn & 63)
                 }
             }
             const uint64_t ms = lballot([&](int b) { const uint32_t i = 64u * w4 + uint32_t(b); return i < nun && lastn[i] != 0u; });
@@ -730,7 +790,7 @@ __global__ void __launch_bounds__(256, 5) k_list_refine(EncCtx c) {   // (five w
         const uint32_t total = lsum32(ntok);
         hist_flush(hist, c.slot_hist + size_t(hist_row) * 256u, freq);
         LFOR(l) if (l == 0) c.slot_raw[cs] = C.runN + C.runH;   // a sign bit per new coefficient, a correction bit per old one
-        if (c.stats_only) continue;   // (nothing is written to the pool)
+        if (c.stats_only || !TOKENS) continue;   // (nothing is written to the pool)
         // ---- room in the pool: one atomic add on the region's cursor
         uint32_t rel = 0;
         LFOR(l) if (l == 0) rel = atomicAdd(&c.tok_cursor[r.region], total);
@@ -748,58 +808,177 @@ __global__ void __launch_bounds__(256, 5) k_list_refine(EncCtx c) {   // (five w
         C.runH = C.runN = C.base = C.prevN = C.prevNZ = 0u;
         uint32_t curc = 0, at = 0;
         for (uint32_t g0 = 0; g0 < ls.n; g0 += 256) {
-            LV<uint32_t> e[4], hex[4], z[4], zp[4], zq[4], cur[4], nt;
+            LV<uint32_t> e[4], hex[4], z[4], zp[4], zq[4];
             LFOR(l) list_load4(ls, g0 + 4u * uint32_t(l), e[0][l], e[1][l], e[2][l], e[3][l]);
             ref_step<true>(e, Ss, Se, C, hex, z, zp, zq);
-            // zq <- the entry's ZRLs | its tokens << 8;  cur: the key of an emitting entry
-            LFOR(l) {
-                uint32_t s = 0;
-                CSH_UNROLL
-                for (int q = 0; q < 4; q++) {
-                    const uint32_t v = e[q][l], blk = (v >> 23) & 255u, lastk = lastn[blk] >> 6, isN = ref_isN(v, Ss, Se);
-                    uint32_t nz = 0, n = 0;
-                    if ((isN | ref_isH(v, Ss, Se)) && (v & 127u) <= lastk) { nz = ((z[q][l] - zp[q][l]) >> 4) - ((zq[q][l] - zp[q][l]) >> 4); n = nz + isN; }
-                    cur[q][l] = n ? ((blk + 1u) << 6) | hex[q][l] : 0u;
-                    if ((v & CSH_NZ_END) && lastk != Se) n = 1u;
-                    zq[q][l] = nz | (n << 8);
-                    s += n;
-                }
-                nt[l] = s;
-            }
-            lscan_last4(cur, curc);
-            uint32_t tot;
-            const LV<uint32_t> ex = lscan(nt, tot);
-            LFOR(l) {
-                uint32_t o = at + ex[l];
-                CSH_UNROLL
-                for (int q = 0; q < 4; q++) {
-                    const uint32_t v = e[q][l], blk = (v >> 23) & 255u, nz = zq[q][l] & 255u, n = zq[q][l] >> 8;
-                    if (!n) continue;
-                    const uint32_t cu = ref_same(cur[q][l], blk);
-                    if (v & CSH_NZ_END) {
-                        if (o < total) tk[o] = TK_EOB | (blk << 3) | ((nh[blk] - cu) << 16) | (cu << 22);
-                        o++;
-                        continue;
-                    }
-                    // the first token takes the correction bits since the block's last emitting entry, the others none
-                    uint32_t cnt = hex[q][l] - cu, from = cu;
-                    for (uint32_t t = 0; t < nz; t++) {
-                        if (o < total) tk[o] = TK_REF | (blk << 3) | (cnt << 16) | (from << 22) | (1u << 28);
-                        o++; cnt = 0u; from = hex[q][l];
-                    }
-                    if (n > nz) {
-                        if (o < total) tk[o] = TK_REF | (blk << 3) | (((z[q][l] - zp[q][l]) & 15u) << 11) | ((v & 128u) ? 0u : (1u << 15)) | (cnt << 16) | (from << 22);
-                        o++;
-                    }
-                }
-            }
-            at += tot;
+            at += ref_step_tokens(e, hex, z, zp, zq, Ss, Se, lastn, nh, curc, tk, at, total);
         }
 #ifdef CSH_EMUL
         if (at != total) { fprintf(stderr, "k_list_refine: pass 2 made %u tokens, pass 1 counted %u\n", at, total); abort(); }
 #endif
     }
     freq_flush(c.tables[r.table_base].freq, freq);
+}
+
+// ---- pack of the refinement scans, from the lists (CSH_REF_PACK): ONE WAVE per run of (scan, chunk) slots, k_list_pack's shape -- the run's table staged once,
+// position, window and code table carried across the chunk edges inside the run, only the run's first and last word ORed into the pool, the byte fill behind
+// the scan's last chunk.  Per chunk the blocks' EOBRUN values, correction words, last N (k_list_refine<false> stored it) and H counts (tail + hex of the last N)
+// go into LDS; then every step of 256 entries is pass 2 of k_list_refine<true> over again -- ref_step<true> and ref_step_tokens, the same statements -- only
+// that the token words go into an LDS buffer of the wave, in list order, and are turned into bits at once, 64 tokens a sub-step, one per lane, through
+// token_main<2> / token_pieces<2> (tok_bits.h: the one statement of what a token emits, k_pack's too).  Most entries of a refinement scan emit nothing (an H
+// entry's correction bit rides behind the block's next token): the tokens are the dense form of the step, and the bit work is done on them, not per entry.
+// Tokens of a step.  Per block: one per N entry, at most 3 ZRLs (z <= 62), one EOB -- at most N + 4 for at least N + 1 entries (its END), and N + 4 > N + 1
+// needs an N: at least 2 entries.  So a block inside the step has at most 2.5 tokens per entry, the two blocks cut by the step's edges at most 3 + 1 more
+// than their entries: 256 x 2.5 + 8 = 648 tokens at most; the buffer holds 704.
+// Bits of a sub-step.  A token emits a symbol of at most 16 bits and a sign bit or at most 14 run bits, then at most 63 correction bits: 30 + 63 = 93 bits --
+// 3 ZRLs, a symbol, a sign bit and 63 correction bits of one entry are 4 of these tokens.  A sub-step is 64 tokens, one per lane: 64 x 93 = 5 952 bits = 186
+// words.  (Small on purpose: the kernel waits on its chain of wave scans, so what counts is how many waves a SIMD holds, and LDS decides that -- 8 KB a wave,
+// 32 KB a workgroup, five workgroups per CU, as k_list_refine.)
+#define CSH_RP_TOKENS 704   // the wave's token buffer, in LDS words (a step of 256 entries makes at most 648 tokens, see above)
+#define CSH_RP_SUB 64       // tokens per sub-step
+#define CSH_RP_WORDS 256    // the window of the bit stream, per wave, in LDS words (a sub-step of 64 tokens adds at most 186, see above)
+#define CSH_RP_STEP 192     // slide when fewer words than this are left behind the complete ones: 1 partial word + 186 + the word lor_bits may touch behind its own
+__global__ void __launch_bounds__(256, 5) k_list_refine_pack(EncCtx c) {   // (five waves per SIMD: what its 32 KB of LDS per workgroup allow)
+    CSH_SHARED alignas(16) uint32_t s_win[4][CSH_RP_WORDS];
+    CSH_SHARED uint32_t s_lut[4][256];
+    CSH_SHARED uint64_t s_corr[4][256];
+    CSH_SHARED uint16_t s_eob[4][256];
+    CSH_SHARED uint16_t s_lastn[4][256];   // per block: its last N, k << 6 | hex (0: no N)
+    CSH_SHARED uint8_t s_nh[4][256];       // per block: its H entries
+    CSH_SHARED uint32_t s_tok[4][CSH_RP_TOKENS];
+    const int wv = int(uni(uint32_t(lwave())));   // (said to be wave-uniform: the run's records are then scalar loads into SGPRs, not a copy per lane in VGPRs)
+    const uint32_t idx = blockIdx.x * 4u + uint32_t(wv);
+    if (idx >= c.nref_runs) return;
+    const uint32_t cs0 = c.ref_runs[idx];
+    const SlotRec r = c.slots[cs0];
+    if (c.work_active && !c.work_active[r.work]) return;
+    const ScanWork &w = c.work[r.work];
+    if (w.no_room) { LFOR(l) if (l == 0) c.status[w.image] = 20200; return; }   // decided per scan by k_scan_place
+    const uint32_t nrun = run_chunks(c, r);
+    const uint64_t lbase = c.nzlists[r.nzlist].base;
+    ListSlot nx = list_chunk(c, lbase, r.nzrec);
+    // the run's place: from bit raw_bit0 of the raw pool on; the scan's last chunk (the last of its run) also carries the 1-bits that fill the last byte
+    const uint64_t scan0 = c.chunk_off[r.first_chunk];
+    const uint64_t raw_bit0 = w.raw_off * 8 + (c.chunk_off[cs0] - scan0);
+    uint32_t pad = 0;
+    if (r.j + nrun == r.nch) { const uint64_t total = c.chunk_off[r.first_chunk + r.nch] - scan0; pad = uint32_t((8 - (total & 7)) & 7); }
+    uint32_t *buf = s_win[wv], *lut = s_lut[wv];
+    uint64_t *corr = s_corr[wv];
+    uint16_t *eobrun = s_eob[wv], *lastn = s_lastn[wv];
+    uint8_t *nh = s_nh[wv];
+    uint32_t *tok = s_tok[wv];
+    LFOR(l) {
+        for (int i = l; i < 256; i += 64) lut[i] = c.tables[r.table_base].lut[i];
+        uint4 zero; zero.x = zero.y = zero.z = zero.w = 0u;
+        for (int i = 4 * l; i < CSH_RP_WORDS; i += 256) *reinterpret_cast<uint4 *>(buf + i) = zero;
+    }
+    CSP_WAVE_SYNC();
+    TokenCtx x;   // the chunk's, out of LDS
+    x.lut = lut; x.lut_stride = 256; x.eobrun = eobrun; x.corr = corr;
+    uint32_t *out = c.raw + (raw_bit0 >> 5);        // word 0 of the frame below
+    uint64_t pos = raw_bit0 & 31u;                   // next bit, in the frame whose word 0 is the run's first word in the pool
+    uint32_t ww = 0;                                 // first word of the window
+    bool first_flush = true;
+    const uint32_t Ss = r.Ss, Se = r.Se;
+    for (uint32_t ci = 0; ci < nrun; ci++) {
+        const ListSlot ls = nx;
+        const bool more = ci + 1u < nrun;
+        if (more) nx = list_chunk(c, lbase, r.nzrec + ci + 1u);
+#ifdef CSH_EMUL
+        {   // (where a pool had no room the pass is repeated and its sizes are not of these lists: even then a run never gets ahead of its sized place -- DESIGN 4.1)
+            const uint64_t want = (raw_bit0 & 31u) + (c.chunk_off[cs0 + ci] - c.chunk_off[cs0]);
+            if (c.overflow[1] ? pos > want : pos != want) { fprintf(stderr, "k_list_refine_pack: chunk %u of a run does not start where the one before it ended\n", ci); abort(); }
+        }
+#endif
+        CSP_WAVE_SYNC();   // (the steps of the chunk before have read what was staged for it)
+        {
+            const uint32_t u0 = r.unit0 + 256u * ci, corr0 = r.corr0 + 256u * ci, left = r.nunits_work - 256u * (r.j + ci), nun = left < 256u ? left : 256u;
+            LFOR(l) for (int i = l; i < 256; i += 64) {
+                const bool in = uint32_t(i) < nun;
+                const uint32_t ln = in ? uint32_t(c.lastn[corr0 + uint32_t(i)]) : 0u;
+                eobrun[i] = in ? c.eobrun[u0 + uint32_t(i)] : uint16_t(0);
+                corr[i] = in ? c.corr[corr0 + uint32_t(i)] : uint64_t(0);
+                lastn[i] = uint16_t(ln);
+                nh[i] = in ? uint8_t(uint32_t(c.tail[u0 + uint32_t(i)]) + (ln & 63u)) : uint8_t(0);
+            }
+        }
+        CSP_WAVE_SYNC();
+        LV<uint32_t> xn[4];   // the next step's entries, asked for a step ahead
+        LFOR(l) list_load4(ls, 4u * uint32_t(l), xn[0][l], xn[1][l], xn[2][l], xn[3][l]);
+        RefCarry C;
+        C.runH = C.runN = C.base = C.prevN = C.prevNZ = 0u;
+        uint32_t curc = 0;
+        for (uint32_t g0 = 0; g0 < ls.n; g0 += 256) {
+            uint32_t ntok;
+            {
+                LV<uint32_t> e[4], hex[4], z[4], zp[4], zq[4];
+                LFOR(l) { e[0][l] = xn[0][l]; e[1][l] = xn[1][l]; e[2][l] = xn[2][l]; e[3][l] = xn[3][l]; }
+                if (g0 + 256u < ls.n) LFOR(l) list_load4(ls, g0 + 256u + 4u * uint32_t(l), xn[0][l], xn[1][l], xn[2][l], xn[3][l]);
+                ref_step<true>(e, Ss, Se, C, hex, z, zp, zq);
+                ntok = ref_step_tokens(e, hex, z, zp, zq, Ss, Se, lastn, nh, curc, tok, 0u, uint32_t(CSH_RP_TOKENS));
+            }
+#ifdef CSH_EMUL
+            if (ntok > CSH_RP_TOKENS) { fprintf(stderr, "k_list_refine_pack: a step of %u tokens\n", ntok); abort(); }
+#endif
+            CSP_WAVE_SYNC();
+            // the step's tokens, 64 at a time, one per lane: the one-piece form first, the three pieces for the whole sub-step where a lane needs them
+            for (uint32_t s0 = 0; s0 < ntok; s0 += CSH_RP_SUB) {
+                LV<uint32_t> t, pv[3], pn[3], slow, len;
+                LFOR(l) {
+                    const uint32_t i = s0 + uint32_t(l);
+                    t[l] = i < ntok ? tok[i] : uint32_t(TK_RAW);   // (an empty RAW token emits nothing)
+                    uint32_t v, n;
+                    slow[l] = token_main<2>(t[l], x, v, n) ? 0u : 1u;
+                    pv[0][l] = v; pn[0][l] = n; pv[1][l] = 0u; pn[1][l] = 0u; pv[2][l] = 0u; pn[2][l] = 0u;
+                }
+                if (lballot([&](int b) { return slow[b] != 0u; })) {
+                    LFOR(l) {
+                        const Pieces p = token_pieces<2>(t[l], x);
+                        CSH_UNROLL
+                        for (int k = 0; k < 3; k++) { pv[k][l] = p.v[k]; pn[k][l] = p.n[k]; }
+                    }
+                }
+                LFOR(l) len[l] = pn[0][l] + pn[1][l] + pn[2][l];
+                uint32_t tot;
+                const LV<uint32_t> ex = lscan(len, tot);
+                LFOR(l) {
+                    uint64_t at = pos + ex[l] - uint64_t(ww) * 32u;    // bit position inside the window
+                    CSH_UNROLL
+                    for (int k = 0; k < 3; k++) if (pn[k][l]) { lor_bits(buf, at, pv[k][l], pn[k][l]); at += pn[k][l]; }
+                }
+                pos += tot;
+                // slide the window when another sub-step's worth of bits might not fit any more
+                const uint32_t done = uint32_t(pos >> 5) - ww;   // complete words in the window
+                if (done > CSH_RP_WORDS - CSH_RP_STEP) {
+                    CSP_WAVE_SYNC();
+                    LFOR(l) for (uint32_t q = uint32_t(l); q < done; q += 64) {
+                        const uint32_t v = buf[q];
+                        if (first_flush && q == 0) { if (v) atomicOr(out + ww, v); } else out[ww + q] = v;
+                    }
+                    const uint32_t partial = buf[done];
+                    CSP_WAVE_SYNC();
+                    LFOR(l) for (int q = l; q < CSH_RP_WORDS; q += 64) buf[q] = (q == 0) ? partial : 0u;
+                    CSP_WAVE_SYNC();
+                    ww += done; first_flush = false;
+                }
+            }
+            CSP_WAVE_SYNC();   // (the next step writes its tokens over these)
+        }
+    }
+    // the byte fill of the scan's last chunk, behind the run's last token (the window has room for a sub-step, and the window is zero behind `pos`)
+    if (pad) { LFOR(l) if (l == 0) lor_bits(buf, pos - uint64_t(ww) * 32u, (1u << pad) - 1u, pad); pos += pad; }
+#ifdef CSH_EMUL
+    {
+        const uint64_t want = (raw_bit0 & 31u) + (c.chunk_off[cs0 + nrun] - c.chunk_off[cs0]) + pad;
+        if (c.overflow[1] ? pos > want : pos != want) { fprintf(stderr, "k_list_refine_pack: a run does not end where its sizes say\n"); abort(); }
+    }
+#endif
+    CSP_WAVE_SYNC();
+    const uint32_t last = uint32_t((pos + 31) >> 5) - ww;   // words in the window that carry bits
+    LFOR(l) for (uint32_t q = uint32_t(l); q < last; q += 64) {
+        const uint32_t v = buf[q];
+        if ((first_flush && q == 0) || q == last - 1) { if (v) atomicOr(out + ww + q, v); } else out[ww + q] = v;
+    }
 }
 
 __global__ void k_reset_works(ScanWork *work, int nwork) {
@@ -815,7 +994,12 @@ void launch_nzlist(hipStream_t st, const EncCtx &c) {
 }
 // one wave per list run, four runs per workgroup
 void launch_list_stats(hipStream_t st, const EncCtx &c) { if (c.nlist_runs) CSH_LAUNCH(k_list_stats, dim3((c.nlist_runs + 3) / 4), dim3(4 * CSP_WAVE_THREADS), st, c); }
-void launch_list_refine(hipStream_t st, const EncCtx &c) { if (c.nref_runs) CSH_LAUNCH(k_list_refine, dim3((c.nref_runs + 3) / 4), dim3(4 * CSP_WAVE_THREADS), st, c); }
+void launch_list_refine(hipStream_t st, const EncCtx &c) {
+    if (!c.nref_runs) return;
+    if (c.ref_pack) CSH_LAUNCH(k_list_refine<false>, dim3((c.nref_runs + 3) / 4), dim3(4 * CSP_WAVE_THREADS), st, c);
+    else CSH_LAUNCH(k_list_refine<true>, dim3((c.nref_runs + 3) / 4), dim3(4 * CSP_WAVE_THREADS), st, c);
+}
+void launch_list_refine_pack(hipStream_t st, const EncCtx &c) { if (c.nref_runs && c.ref_pack) CSH_LAUNCH(k_list_refine_pack, dim3((c.nref_runs + 3) / 4), dim3(4 * CSP_WAVE_THREADS), st, c); }
 void launch_list_pack(hipStream_t st, const EncCtx &c) { if (c.nlist_runs) CSH_LAUNCH(k_list_pack, dim3((c.nlist_runs + 3) / 4), dim3(4 * CSP_WAVE_THREADS), st, c); }
 // ---- the slots of the work items: one workgroup per work item, one lane per 256-unit chunk.  Under the scan search a 1080p image has ~3.9 k slots in 58 work
 // items: built on the host they were 64 MB of records per 256 files to write and to upload in front of the first kernel (the boundary call paid ~15 ms of
@@ -828,7 +1012,7 @@ __global__ void __launch_bounds__(64) k_make_slots(const ScanWork *works, uint32
     const EncScan &e = script[w.scan];
     const uint32_t nch = (w.nunits + 255u) / 256u;
     const bool prog_ac = e.Ss > 0 && !e.sequential, has_list = w.list != 0xFFFFFFFFu;
-    const bool ref_list = has_list && prog_ac && e.Ah;   // a refinement scan coded from its list: k_list_refine makes its tokens, k_pack packs them
+    const bool ref_list = has_list && prog_ac && e.Ah;   // a refinement scan coded from its list: k_list_refine, then k_list_refine_pack or (CSH_REF_PACK=0) k_pack over its tokens
     const bool listed = has_list && !ref_list;
     for (uint32_t j = threadIdx.x; j < nch; j += blockDim.x) {
         SlotRec r;
@@ -841,7 +1025,7 @@ __global__ void __launch_bounds__(64) k_make_slots(const ScanWork *works, uint32
         r.nzlist = has_list ? w.list : 0u; r.nzrec = has_list ? nzlists[w.list].chunk0 + j : 0u; r.region = ref_list ? w.region : 0u;
         slots[w.first_chunk + j] = r;
         slot_work[w.first_chunk + j] = wi;
-        (listed ? list_slots : tok_slots)[w.ls_base + j] = w.first_chunk + j;
+        if (w.ls_base != 0xFFFFFFFFu) (listed ? list_slots : tok_slots)[w.ls_base + j] = w.first_chunk + j;   // (none: a refinement scan packed from its list)
         if (ref_list) ref_slots[w.rs_base + j] = w.first_chunk + j;
         // the list runs (k_list_stats, k_list_pack / k_list_refine): the first slot of every run of list_run chunks; the last run of a work item is as long as what is left
         if (listed && j % list_run == 0u) list_runs[w.lr_base + j / list_run] = w.first_chunk + j;

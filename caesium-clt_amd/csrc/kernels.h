@@ -169,7 +169,7 @@ struct EncCtx {  // device pointers + sizes every entropy kernel needs
     uint16_t *nz_blk_off;      // null, or (the same lists) per block: where its first entry stands in its chunk -- k_trellis_ac writes the levels it chose into the entries
     const uint32_t *list_slots;// the run's slots that are coded from a list (k_list_stats, k_list_pack) ...
     uint32_t nlist_slots;
-    const uint32_t *tok_slots; // ... and those packed from tokens (k_pack); null: every slot of [slot0, slot0 + nslots)
+    const uint32_t *tok_slots; // ... and those packed from tokens (k_pack); null: every slot of [slot0, slot0 + nslots).  (Under ref_pack the refinement slots are in neither list: ref_runs)
     uint32_t ntok_slots;
     const uint32_t *ref_slots; // those of the token-coded slots that are refinement scans coded from their list: k_list_refine writes their tokens (k_tokens does not)
     uint32_t nref_slots;
@@ -180,6 +180,9 @@ struct EncCtx {  // device pointers + sizes every entropy kernel needs
     const uint32_t *ref_runs;
     uint32_t nref_runs;
     uint32_t list_run;         // CSH_LIST_RUN, 1..32
+    uint16_t *lastn;           // per unit of a refinement scan, indexed like corr[] (CSH_REF_PACK): the block's last newly significant coefficient, k << 6 | its H entries in
+                               // front of it (0: none) -- k_list_refine<false> writes it, k_list_refine_pack reads it
+    uint32_t ref_pack;         // CSH_REF_PACK: the refinement scans coded from lists are packed from the lists too (k_list_refine_pack); 0: tokens and k_pack
     uint32_t ac_runs_slot;     // CSH_AC_RUNS=slot: launch_ac_runs takes k_ac_runs (one wave per slot), not k_ac_runs_words (one per 16 slots)
     uint32_t nz_build, nz_filter; // the run's NzChunks: some asks for level 0 from the tiles (k_nzlist) / for a filtered level (k_nzfilter); a kernel nobody asks for is not launched
 };
@@ -194,8 +197,9 @@ void launch_pack(hipStream_t st, const EncCtx &c);
 // counts, has-symbol / ends-with-EOB flags) of the run's list slots -- in launch_tokens' place --; their bits -- in launch_pack's place
 void launch_nzlist(hipStream_t st, const EncCtx &c);
 void launch_list_stats(hipStream_t st, const EncCtx &c);
-void launch_list_refine(hipStream_t st, const EncCtx &c);   // tokens, flags and statistics of the run's refinement slots (EncCtx::ref_slots) -- in k_tokens' place
+void launch_list_refine(hipStream_t st, const EncCtx &c);   // flags, statistics and (EncCtx::ref_pack == 0) tokens of the run's refinement slots (EncCtx::ref_slots) -- in k_tokens' place
 void launch_list_pack(hipStream_t st, const EncCtx &c);
+void launch_list_refine_pack(hipStream_t st, const EncCtx &c);   // the bits of the run's refinement slots, from the lists (EncCtx::ref_pack) -- in launch_pack's place
 // the debug tap's way back (csh_batch_read_coefs): the AC coefficients of component `set`, whose levels the last run kept in its level-0 list alone
 // (PlaneWork::ac_lists), written into its tiles again -- every block's AC zeroed, then the list's entries scattered; the DC stays.  Off the hot path
 void launch_nz_to_tiles(hipStream_t st, const NzSet *nzsets, const NzList *nzlists, const uint32_t *nz_pool, const uint32_t *nz_chunk_off, const uint32_t *nz_chunk_cnt,

@@ -273,6 +273,7 @@ static int batch_run(csh_batch *b, csh_timing *t, bool requant_only) {
         t->n_list_refine = b->enc.last_run_refine;
         t->n_ac_in_lists = b->enc.last_run_ac_lists;
         t->n_list_runs = b->enc.last_run_list_runs;
+        t->n_ref_packed = b->enc.last_run_ref_packed;
         for (const Item &it : b->items) if (it.image < 0) t->n_failed++;
         for (int i = 0; i < b->nimg; i++) { t->out_bytes += b->out.h_img_size[i]; t->pixels += uint64_t(b->imgs[i].width) * b->imgs[i].height; }
         t->in_bytes = b->dec.bits_pool.size();

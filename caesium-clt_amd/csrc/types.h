@@ -224,7 +224,7 @@ struct ScanWork {
     uint32_t corr_base;    // refinement scans: the scan's first correction word in EncCtx::corr (one u64 per unit of a REFINEMENT scan only: 8 bytes for every unit of
                            // every candidate scan were 7.5 MB of a 1080p picture's 37 MB of pools); 0xFFFFFFFF otherwise
     uint32_t hist_row0;    // first histogram row of its first slot (slot j: hist_row0 + j * ntables)
-    uint32_t ls_base;      // where its slots stand in the list of list-coded slots (first-pass scans with a list) or of token-coded slots
+    uint32_t ls_base;      // where its slots stand in the list of list-coded slots (first-pass scans with a list) or of token-coded slots; 0xFFFFFFFF: in neither (a refinement scan packed from its list)
     uint32_t rs_base;      // refinement scans coded from their list (k_list_refine): where its slots stand in the list of such slots; 0xFFFFFFFF otherwise
     uint32_t region;       // ... and the region of the token pool their tokens go to (one per image, component and stage)
     uint32_t lr_base;      // first-pass scans with a list: where its runs of CSH_LIST_RUN chunks stand in the list of list runs (EncCtx::list_runs)

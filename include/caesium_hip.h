@@ -143,6 +143,8 @@ typedef struct {
     uint32_t n_list_runs;         /* waves' worth of work of the list kernels in this run: the runs of up to CSH_LIST_RUN (1..32) consecutive 256-block chunks that the progressive AC
                                      work items this run coded from the coefficient lists were cut into -- the sum of ceil(chunks / CSH_LIST_RUN) over them, all stages (the trellis
                                      quantiser's statistics scans and the scan search's candidates included).  0 for sequential output */
+    uint32_t n_ref_packed;        /* of n_list_refine, the work items whose bits this run packed from the lists as well (k_list_refine_pack): no token was written for them.
+                                     0 with CSH_REF_PACK=0 (tokens and k_pack, as before), with CSH_REF_LIST=0 and for sequential output */
 } csh_timing;
 
 int csh_device_count(void);
