@@ -34,6 +34,11 @@ class PngTiming(C.Structure):
                 ("raw_bytes", C.c_uint64), ("n_images", C.c_uint32), ("n_failed", C.c_uint32), ("n_trials", C.c_uint32)]
 
 
+class GifTiming(C.Structure):
+    _fields_ = [("total_ms", C.c_float), ("kernel_ms", C.c_float * 8), ("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("n_files", C.c_uint32), ("n_frames", C.c_uint32),
+                ("n_failed", C.c_uint32), ("n_passed_palette", C.c_uint32), ("n_not_smaller", C.c_uint32), ("chunk_pixels", C.c_uint32)]
+
+
 class CaesiumError(RuntimeError):
     def __init__(self, code, message):
         super().__init__(f"[{code}] {message}")
@@ -50,6 +55,8 @@ EXPORTS = ["cs_default_parameters", "cs_compress_in_memory", "cs_compress_to_siz
            "csp_kernel_name", "csp_batch_create", "csp_batch_create_webp", "csp_batch_create_pixels", "csh_batch_create_pixels", "csh_batch_pixels", "csh_batch_create_from_pixels", "csp_png_to_jpeg", "csp_png_to_lossless_webp", "csp_batch_run", "csp_batch_fetch", "csp_batch_destroy", "csp_batch_geometry", "csp_batch_read_rows", "csp_batch_read_stream",
            "csp_batch_trials", "csp_batch_read_scores", "csp_batch_chunk_bits", "csh_batch_create_webp", "cs_batch_convert",
            "cswd_batch_create", "cswd_batch_run", "cswd_batch_pixels", "cswd_batch_read_pixels", "cswd_batch_alpha", "cswd_batch_read_rgba", "cswd_batch_destroy", "cswd_batch_frames", "cswd_batch_read_canvas", "cswd_batch_encode_anim", "cswd_rgba_join", "cswd_rgba_destroy", "csh_batch_create_webp_from_pixels", "csh_batch_create_from_pixels_rgb", "csl_encode_pixels", "csl_attach_alpha"]
+# the GIF batch's entry points (the csg_ prefix): a list of their own, beside the one above
+GIF_EXPORTS = ["csg_kernel_name", "csg_batch_create", "csg_batch_run", "csg_batch_fetch", "csg_batch_destroy", "csg_batch_frames", "csg_batch_read_indices", "csg_batch_read_canvas"]
 
 
 def _declare(L):
@@ -115,6 +122,16 @@ def _declare(L):
     L.cswd_rgba_join.restype = C.c_int
     L.cswd_rgba_destroy.argtypes = [C.c_void_p]
     L.cswd_rgba_destroy.restype = None
+    L.csg_kernel_name.argtypes = [C.c_int]
+    L.csg_kernel_name.restype = C.c_char_p
+    L.csg_batch_create.argtypes = [P(CByteArray), C.c_size_t, P(CCSParameters), C.c_int, P(C.c_void_p)]
+    L.csg_batch_run.argtypes = [C.c_void_p, P(GifTiming)]
+    L.csg_batch_fetch.argtypes = [C.c_void_p, P(CByteArray), P(CCSResult)]
+    L.csg_batch_destroy.argtypes = [C.c_void_p]
+    L.csg_batch_destroy.restype = None
+    L.csg_batch_frames.argtypes = [C.c_void_p, C.c_size_t, P(C.c_uint32), P(C.c_uint32), P(C.c_uint32)]
+    L.csg_batch_read_indices.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
+    L.csg_batch_read_canvas.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
     return L
 
 
@@ -306,6 +323,80 @@ class PngBatch:
             pass
 
 
+class GifBatch:
+    """csg_batch: a group of GIF files, decoded, composed and coded again on the device (the route CSH_GIF=device selects)."""
+
+    def __init__(self, api, blobs, params, device=0):
+        self.api = api
+        L = api.L
+        self.n = len(blobs)
+        self._keep = [C.create_string_buffer(b, len(b)) for b in blobs]
+        self._in = (CByteArray * self.n)()
+        for i, buf in enumerate(self._keep):
+            self._in[i].data = C.cast(buf, C.POINTER(C.c_uint8))
+            self._in[i].length = len(blobs[i])
+        self.h = C.c_void_p()
+        rc = L.csg_batch_create(self._in, self.n, C.byref(params), device, C.byref(self.h))
+        if rc:
+            raise CaesiumError(rc, L.csh_last_error().decode())
+
+    def run(self):
+        t = GifTiming()
+        rc = self.api.L.csg_batch_run(self.h, C.byref(t))
+        if rc:
+            raise CaesiumError(rc, self.api.L.csh_last_error().decode())
+        return t
+
+    def fetch(self):
+        L = self.api.L
+        outs = (CByteArray * self.n)()
+        res = (CCSResult * self.n)()
+        if L.csg_batch_fetch(self.h, outs, res) < 0:
+            raise CaesiumError(-1, L.csh_last_error().decode())
+        result = []
+        for i in range(self.n):
+            result.append(C.string_at(outs[i].data, outs[i].length) if res[i].success else CaesiumError(res[i].code, (res[i].error_message or b"").decode()))
+            L.cs_free_bytes(C.byref(outs[i])); L.cs_free_result(C.byref(res[i]))
+        return result
+
+    def frames(self, file):
+        """-> (frame count, canvas width, canvas height); CaesiumError for a file that failed"""
+        nf, w, h = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        rc = self.api.L.csg_batch_frames(self.h, file, C.byref(nf), C.byref(w), C.byref(h))
+        if rc:
+            raise CaesiumError(rc, "the file failed" if rc > 0 else self.api.L.csh_last_error().decode())
+        return nf.value, w.value, h.value
+
+    def indices(self, file, frame, w, h):
+        """frame `frame`'s decoded rectangle: [h][w] colour indices in row order"""
+        import numpy as np
+        a = np.empty((h, w), dtype=np.uint8)
+        rc = self.api.L.csg_batch_read_indices(self.h, file, frame, a.ctypes.data)
+        if rc:
+            raise CaesiumError(rc, self.api.L.csh_last_error().decode())
+        return a
+
+    def canvas(self, file, frame):
+        import numpy as np
+        nf, w, h = self.frames(file)
+        a = np.empty((h, w, 4), dtype=np.uint8)
+        rc = self.api.L.csg_batch_read_canvas(self.h, file, frame, a.ctypes.data)
+        if rc:
+            raise CaesiumError(rc, self.api.L.csh_last_error().decode())
+        return a
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.api.L.csg_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class CaesiumHip:
     def __init__(self, path=None):
         path = path or library_path()
@@ -442,6 +533,30 @@ class CaesiumHip:
             return out
         finally:
             L.cswd_batch_destroy(h)
+
+    def gif_batch(self, blobs, params=None, device=0):
+        return GifBatch(self, blobs, params or default_parameters(), device)
+
+    def gif_kernel_names(self):
+        return [self.L.csg_kernel_name(i).decode() for i in range(8)]
+
+    def gif_canvases(self, blobs, device=0):
+        """GIF files -> per file an array [frames][H][W][4] uint8: every canvas as the device walk composes it (transparent index and disposal applied, 0 where
+        nothing was painted); a CaesiumError per file that fails or is passed through unread (a plain-text extension)"""
+        import numpy as np
+        b = self.gif_batch(blobs, None, device)
+        try:
+            b.run()
+            out = []
+            for i in range(len(blobs)):
+                try:
+                    nf, w, h = b.frames(i)
+                    out.append(np.stack([b.canvas(i, k) for k in range(nf)]))
+                except CaesiumError as e:
+                    out.append(e)
+            return out
+        finally:
+            b.close()
 
     def webp_batch(self, blobs, params, device=0):
         """JPEG in, WebP out: the same batch object with the VP8 encoder as its tail"""

@@ -36,6 +36,7 @@ uint64_t webp_declared_pixels(const uint8_t *d, size_t n) {
 static uint64_t declared_pixels(const uint8_t *d, size_t n) {
     if (n >= 30 && !memcmp(d, "RIFF", 4)) return route::webp_declared_pixels(d, n);
     if (n >= 24 && !memcmp(d, "\x89PNG\r\n\x1a\n", 8)) return route::png_declared_pixels(d);
+    if (n >= 13 && !memcmp(d, "GIF8", 4)) return csg_declared_pixels(d, n);
     if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return 0;
     for (size_t i = 2; i + 4 <= n;) {
         if (d[i] != 0xFF) { i++; continue; }
@@ -55,6 +56,8 @@ static uint64_t declared_pixels(const uint8_t *d, size_t n) {
 // passthrough") are passed through: the file comes back as it is, with Success -- as for a PNG that oxipng cannot make smaller.  A tree
 // that holds such files (configs[4], /root/reference/src/compressor.rs:774 hands the engine a .tif) then completes without error lines; the
 // caller's overwrite / min-savings policy sees equal sizes and acts on that.  A resize or a conversion of such a file is still refused.
+// A GIF file leaves this path under CSH_GIF=device (read on every call; unset, empty or "pass": here as before): route::gif_compress optimises it, pixel-exact
+// (DESIGN.md 8.3); its resize is still answered here, and any other value of the variable fails the call's GIF files with CS_ERR_UNSUPPORTED.
 static CCSResult passthrough(const CByteArray &in, const CCSParameters *p, CByteArray *out) {
     out->data = nullptr; out->length = 0;
     if (p->width || p->height) return make_result(CS_ERR_UNSUPPORTED, "resizing a GIF / TIFF file has no path in this build (the file itself is passed through without a size)");
@@ -63,20 +66,32 @@ static CCSResult passthrough(const CByteArray &in, const CCSParameters *p, CByte
     memcpy(out->data, in.data, in.length); out->length = in.length;
     return make_result(0, nullptr);
 }
-// the files of a compress call by the row that takes them; a GIF / TIFF file is answered on the spot, by pass(i)
-struct Rows { std::vector<size_t> png, webp, other; bool any_pass = false; };
-template <class Pass>
-static Rows sort_rows(const CByteArray *inputs, size_t count, Pass pass) {
+// CSH_GIF: 0 pass the file through, 1 the device route, -1 a value that names neither
+static int gif_mode() {
+    const char *e = getenv("CSH_GIF");
+    if (!e || !*e || !strcmp(e, "pass")) return 0;
+    return !strcmp(e, "device") ? 1 : -1;
+}
+// the files of a compress call by the row that takes them; a TIFF file, and a GIF file outside CSH_GIF=device, is answered on the spot, by pass(i) -- or by
+// refuse(i) under a value of CSH_GIF that means nothing
+struct Rows { std::vector<size_t> png, webp, gif, other; bool any_pass = false; };
+template <class Pass, class Refuse>
+static Rows sort_rows(const CByteArray *inputs, size_t count, const CCSParameters *p, Pass pass, Refuse refuse) {
     Rows r;
+    const int gif = gif_mode();
     for (size_t i = 0; i < count; i++) {
         const int t = sniff(inputs[i].data, inputs[i].length);
-        if (t == CS_TYPE_GIF || t == CS_TYPE_TIFF) { pass(i); r.any_pass = true; }
+        if (t == CS_TYPE_GIF && gif < 0) { refuse(i); r.any_pass = true; }
+        else if (t == CS_TYPE_GIF && gif > 0 && !p->width && !p->height) r.gif.push_back(i);
+        else if (t == CS_TYPE_GIF || t == CS_TYPE_TIFF) { pass(i); r.any_pass = true; }
         else (t == CS_TYPE_PNG ? r.png : t == CS_TYPE_WEBP ? r.webp : r.other).push_back(i);
     }
     return r;
 }
 
 // A caller may pass no results array: the routes always write one, so such a call gets an array of its own here, released when the call returns
+static const char *const BAD_CSH_GIF = "CSH_GIF names no GIF path (unset, empty or \"pass\": the file is passed through; \"device\": the pixel-exact optimiser)";
+
 struct Results {
     std::vector<CCSResult> own;
     CCSResult *r;
@@ -141,19 +156,22 @@ int cs_batch_compress(const CByteArray *inputs, size_t count, const CCSParameter
     Results own(results_or_null, count);
     CCSResult *results = own.r;
     int passed_failed = 0;
-    const Rows r = sort_rows(inputs, count, [&](size_t i) { results[i] = passthrough(inputs[i], p, &outputs[i]); if (!results[i].success) passed_failed++; });
-    const std::vector<size_t> &png = r.png, &webp = r.webp, &other = r.other;   // PNG files: lossless under png.optimize, else the lossy (quantising) form of the same pipeline
-    if (png.empty() && webp.empty() && !r.any_pass) return route::jpeg_compress(inputs, count, p, device, outputs, results);
+    const Rows r = sort_rows(inputs, count, p, [&](size_t i) { results[i] = passthrough(inputs[i], p, &outputs[i]); if (!results[i].success) passed_failed++; },
+                             [&](size_t i) { outputs[i].data = nullptr; outputs[i].length = 0; results[i] = make_result(CS_ERR_UNSUPPORTED, BAD_CSH_GIF); passed_failed++; });
+    const std::vector<size_t> &png = r.png, &webp = r.webp, &gif = r.gif, &other = r.other;   // PNG files: lossless under png.optimize, else the lossy (quantising) form of the same pipeline
+    if (png.empty() && webp.empty() && gif.empty() && !r.any_pass) return route::jpeg_compress(inputs, count, p, device, outputs, results);
     std::atomic<int> failed{0};
     auto run = [&](const std::vector<size_t> &idx, int kind) {
         failed += route::for_subset(inputs, idx, outputs, results, [&](const CByteArray *in, size_t n, CByteArray *out, CCSResult *res) {
-            return kind == 1 ? route::png_compress(in, n, p, device, out, res, false) : kind == 2 ? route::webp_inputs(in, n, p, CS_TYPE_WEBP, device, out, res) : route::jpeg_compress(in, n, p, device, out, res);
+            return kind == 1 ? route::png_compress(in, n, p, device, out, res, false) : kind == 2 ? route::webp_inputs(in, n, p, CS_TYPE_WEBP, device, out, res) :
+                   kind == 3 ? route::gif_compress(in, n, p, device, out, res) : route::jpeg_compress(in, n, p, device, out, res);
         });
     };
-    // the three rows side by side (each batch keeps to its own stream; their outputs are disjoint): a tree of all three kinds waits for its slowest row only
+    // the rows side by side (each batch keeps to its own stream; their outputs are disjoint): a tree of all three kinds waits for its slowest row only
     std::vector<std::thread> rows;
     if (!png.empty() && (!webp.empty() || !other.empty())) rows.emplace_back(run, std::cref(png), 1); else run(png, 1);
     if (!webp.empty() && !other.empty()) rows.emplace_back(run, std::cref(webp), 2); else run(webp, 2);
+    if (!gif.empty() && !other.empty()) rows.emplace_back(run, std::cref(gif), 3); else run(gif, 3);
     run(other, 0);
     for (std::thread &t : rows) t.join();
     return failed.load() + passed_failed;
@@ -171,18 +189,20 @@ int cs_batch_compress_to_size(const CByteArray *inputs, size_t count, CCSParamet
     Results own(results_or_null, count);
     CCSResult *results = own.r;
     int failed = 0;
-    const Rows rows = sort_rows(inputs, count, [&](size_t i) {   // passed through as it is (see passthrough()): there is no quality to walk
-        CCSResult &r = results[i];
-        r = passthrough(inputs[i], p, &outputs[i]);
-        // libcaesium's size walk returns its smallest try when asked to, and fails otherwise: a file that cannot be made smaller
-        // and is larger than the target is a failure unless return_smallest
-        if (r.success && outputs[i].length > max_output_size && !return_smallest) {
-            cs_free_bytes(&outputs[i]);
-            r = make_result(CS_ERR_TOO_BIG, "the file is passed through as it is (GIF / TIFF have no device path) and is larger than the target size");
-        }
-        if (!r.success) failed++;
-    });
-    if (rows.png.empty() && rows.webp.empty() && !rows.any_pass) return route::jpeg_compress_to_size(inputs, count, p, max_output_size, return_smallest, device, outputs, results);
+    // libcaesium's size walk returns its smallest try when asked to, and fails otherwise: a file that cannot be made smaller
+    // and is larger than the target is a failure unless return_smallest
+    auto hold_to_target = [&](size_t i, const char *msg) {
+        if (results[i].success && outputs[i].length > max_output_size && !return_smallest) { cs_free_bytes(&outputs[i]); results[i] = make_result(CS_ERR_TOO_BIG, msg); failed++; }
+    };
+    const Rows rows = sort_rows(inputs, count, p, [&](size_t i) {   // passed through as it is (see passthrough()): there is no quality to walk
+        results[i] = passthrough(inputs[i], p, &outputs[i]);
+        if (!results[i].success) failed++;
+        hold_to_target(i, "the file is passed through as it is (GIF / TIFF have no device path) and is larger than the target size");
+    }, [&](size_t i) { outputs[i].data = nullptr; outputs[i].length = 0; results[i] = make_result(CS_ERR_UNSUPPORTED, BAD_CSH_GIF); failed++; });
+    // a GIF file under CSH_GIF=device: one run of its route (the optimiser is pixel-exact: there is no quality to walk), then the same rule
+    failed += route::for_subset(inputs, rows.gif, outputs, results, [&](const CByteArray *in, size_t n, CByteArray *out, CCSResult *res) { return route::gif_compress(in, n, p, device, out, res); });
+    for (size_t i : rows.gif) hold_to_target(i, "the GIF optimiser is pixel-exact and has no quality to walk: its one result is larger than the target size");
+    if (rows.png.empty() && rows.webp.empty() && rows.gif.empty() && !rows.any_pass) return route::jpeg_compress_to_size(inputs, count, p, max_output_size, return_smallest, device, outputs, results);
     // the JPEG walk leaves its last quality in the caller's parameters, as the reference's &mut does
     failed += route::for_subset(inputs, rows.other, outputs, results, [&](const CByteArray *in, size_t n, CByteArray *out, CCSResult *res) {
         return route::jpeg_compress_to_size(in, n, p, max_output_size, return_smallest, device, out, res);

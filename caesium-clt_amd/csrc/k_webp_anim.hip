@@ -14,34 +14,10 @@ namespace csw {
 
 using csh::LV;
 using csh::lballot;
+using csh::lmax32;
+using csh::lmin32;
 
 enum : uint32_t { ANIM_PX = 4, ANIM_TILE = 64 * ANIM_PX };
-
-// minimum / maximum over the lanes, in every lane (all 64 lanes active)
-__device__ __forceinline__ static uint32_t lmin32(const LV<uint32_t> &x) {
-#ifdef CSH_EMUL
-    uint32_t m = x.v[0];
-    for (int j = 1; j < 64; j++) m = x.v[j] < m ? x.v[j] : m;
-    return m;
-#else
-    uint32_t v = x.v;
-    CSH_UNROLL
-    for (int o = 32; o >= 1; o >>= 1) { const uint32_t y = uint32_t(__shfl_xor(int(v), o, 64)); v = y < v ? y : v; }
-    return v;
-#endif
-}
-__device__ __forceinline__ static uint32_t lmax32(const LV<uint32_t> &x) {
-#ifdef CSH_EMUL
-    uint32_t m = x.v[0];
-    for (int j = 1; j < 64; j++) m = x.v[j] > m ? x.v[j] : m;
-    return m;
-#else
-    uint32_t v = x.v;
-    CSH_UNROLL
-    for (int o = 32; o >= 1; o >>= 1) { const uint32_t y = uint32_t(__shfl_xor(int(v), o, 64)); v = y > v ? y : v; }
-    return v;
-#endif
-}
 
 // a pixel is R | G << 8 | B << 16 | A << 24: the RGBA bytes of the pools as one little-endian word
 // AnimDecoder's blend of a source pixel over the canvas, neither premultiplied

@@ -54,6 +54,32 @@ __device__ __forceinline__ static uint32_t lsum32(const LV<uint32_t> &x) {
     (void)lscan(x, s);
     return s;
 }
+// minimum / maximum over the lanes, in every lane (all 64 lanes active)
+__device__ __forceinline__ static uint32_t lmin32(const LV<uint32_t> &x) {
+#ifdef CSH_EMUL
+    uint32_t m = x.v[0];
+    for (int j = 1; j < 64; j++) m = x.v[j] < m ? x.v[j] : m;
+    return m;
+#else
+    uint32_t v = x.v;
+    CSH_UNROLL
+    for (int o = 32; o >= 1; o >>= 1) { const uint32_t y = uint32_t(__shfl_xor(int(v), o, 64)); v = y < v ? y : v; }
+    return v;
+#endif
+}
+__device__ __forceinline__ static uint32_t lmax32(const LV<uint32_t> &x) {
+#ifdef CSH_EMUL
+    uint32_t m = x.v[0];
+    for (int j = 1; j < 64; j++) m = x.v[j] > m ? x.v[j] : m;
+    return m;
+#else
+    uint32_t v = x.v;
+    CSH_UNROLL
+    for (int o = 32; o >= 1; o >>= 1) { const uint32_t y = uint32_t(__shfl_xor(int(v), o, 64)); v = y > v ? y : v; }
+    return v;
+#endif
+}
+
 // inclusive maximum scan over the lanes (all 64 lanes active)
 __device__ __forceinline__ static LV<uint32_t> lmaxscan(const LV<uint32_t> &x) {
     LV<uint32_t> r;

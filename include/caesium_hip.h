@@ -41,6 +41,7 @@ enum {
     CS_ERR_POOL_OVERFLOW = 20200,  /* internal device pool too small even after retry */
     CS_ERR_BAD_PNG = 30100,        /* malformed / truncated PNG (chunk walk, zlib stream, filter bytes) */
     CS_ERR_BAD_WEBP = 40100,       /* malformed / truncated WebP (RIFF chunk walk, VP8 frame header, bool-coded data running out) */
+    CS_ERR_BAD_GIF = 50100,        /* malformed / truncated GIF (block walk, a rectangle that leaves the canvas, LZW code size or codes, data that ends early); only under CSH_GIF=device */
     CS_ERR_SAME_FORMAT = 10407,    /* convert_in_memory: source type == target type */
     CS_ERR_TOO_BIG = 10500         /* compress_to_size: cannot reach max_output_size */
 };
@@ -287,6 +288,42 @@ void cswd_rgba_destroy(cswd_rgba *r);
 int csh_batch_create_webp_from_pixels(const struct csp_pixels_s *sources, size_t count, const CCSParameters *p, int device, csh_batch **out);
 /* pixels in, resized pixels out (csh_batch_pixels): the Lanczos branch alone */
 int csh_batch_create_from_pixels_rgb(const struct csp_pixels_s *sources, size_t count, const CCSParameters *p, int device, csh_batch **out);
+
+
+/* ------------------------------------------------------------------------------------------------
+ * GIF INPUTS (libcaesium: gifski, a lossy re-quantiser).  Built here: a pixel-exact optimiser -- every canvas the output renders equals the canvas the input
+ * renders; frame 0 is the whole canvas, every later frame the bounding box of what changed, unchanged pixels are written as the frame's transparent index, the LZW
+ * streams are coded afresh (DESIGN.md 8.3 states the rule byte for byte).  Colour tables, delays, the loop extension and the screen descriptor are the input's;
+ * comment and other application extensions are kept under keep_metadata only; gif_quality is read and ignored.  A file that does not get smaller, a file with a
+ * plain-text extension and a file whose frames would need a colour their own table lacks come back as they are.
+ * cs_batch_compress and cs_batch_compress_to_size route GIF files here when CSH_GIF=device is in the environment, read on EVERY call: unset, empty or "pass" = the
+ * file is passed through as before; any other value fails every GIF of the call with CS_ERR_UNSUPPORTED and a message that names the variable.  A resize or a
+ * conversion from or to GIF stays refused.  CSH_GIF_CHUNK (1024..1048576, default 16384): the pixels of an output frame one wave codes from an empty table.
+ */
+typedef struct csg_batch csg_batch;
+enum { CSG_NKERNELS = 8 };
+typedef struct {
+    float total_ms;                  /* hipEvent time from the first launch to the last, on the batch's stream */
+    float kernel_ms[CSG_NKERNELS];   /* names: csg_kernel_name */
+    uint64_t in_bytes, out_bytes;    /* LZW bytes in, file bytes out (the device's result for every file it coded, before the "not smaller" rule) */
+    uint32_t n_files, n_frames, n_failed;
+    uint32_t n_passed_palette;       /* files passed through because a frame would have to paint a colour its table lacks, or leave alone a pixel it cannot, or has a transparent
+                                        index its output code size cannot code */
+    uint32_t n_not_smaller;          /* files passed through because the coded file is not smaller */
+    uint32_t chunk_pixels;           /* CSH_GIF_CHUNK as this batch read it */
+} csg_timing;
+const char *csg_kernel_name(int slot);
+/* inputs are borrowed until csg_batch_destroy */
+int csg_batch_create(const CByteArray *inputs, size_t count, const CCSParameters *p, int device, csg_batch **out);
+int csg_batch_run(csg_batch *b, csg_timing *t);
+int csg_batch_fetch(csg_batch *b, CByteArray *outputs, CCSResult *results);
+void csg_batch_destroy(csg_batch *b);
+/* stage taps for the tests.  csg_batch_frames: the file's code if it failed, else 0 with the frame count and the canvas.  After csg_batch_run:
+   csg_batch_read_indices: frame `frame`'s decoded rectangle, w * h colour indices in row order (de-interlaced); csg_batch_read_canvas: canvas `frame` as the
+   walk composes it (disposals applied, 0x00000000 where nothing was painted), canvas_w * canvas_h * 4 bytes of RGBA, rebuilt on the device for the call */
+int csg_batch_frames(csg_batch *b, size_t file, uint32_t *nframes, uint32_t *canvas_w, uint32_t *canvas_h);
+int csg_batch_read_indices(csg_batch *b, size_t file, uint32_t frame, uint8_t *dst);
+int csg_batch_read_canvas(csg_batch *b, size_t file, uint32_t frame, uint8_t *dst_rgba);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,55 @@
+"""GIF inputs under CSH_GIF=device on the MI355X: the cases of tests/test_gif_emul.py through the product library (the decoder's and the composer's taps against
+the model, the optimiser's bytes against the Python statement of its rule, fallbacks, errors, routing, the CLI)."""
+import os
+
+import pytest
+
+import test_gif_emul as E
+from _util import ROOT, product_api
+
+pytestmark = [pytest.mark.gpu, pytest.mark.timeout(600, method="thread")]
+PRODUCT_CLI = os.path.join(ROOT, "caesium-clt_amd", "bin", "caesiumclt")
+
+
+@pytest.fixture(scope="module")
+def api():
+    a = product_api()
+    assert a.device_count() >= 1, "no HIP device: libcaesium_hip has no CPU path"
+    return a
+
+
+def test_decoder_tap_equals_the_model(api):
+    E.check_decoder(api)
+
+
+def test_canvas_tap_equals_the_model_and_pillow(api):
+    E.check_canvases(api)
+
+
+def test_outputs_equal_the_model_and_render_the_input(api):
+    E.test_emul_outputs_equal_the_model_and_render_the_input(api)
+
+
+def test_chunk_seams_and_the_bit_merge(api, monkeypatch):
+    E.test_emul_chunk_seams_and_the_bit_merge(api, monkeypatch)
+
+
+def test_metadata_is_kept_under_keep_metadata_only(api):
+    E.test_emul_metadata_is_kept_under_keep_metadata_only(api)
+
+
+def test_fallbacks_return_the_input(api):
+    E.check_fallbacks(api)
+
+
+def test_malformed_files_fail_alone(api):
+    E.check_malformed(api)
+
+
+def test_routing_under_each_setting(api, monkeypatch):
+    E.check_routing(api, monkeypatch)
+
+
+def test_cli_writes_the_smaller_file(api, tmp_path):
+    assert os.path.exists(PRODUCT_CLI), "caesium-clt_amd/bin/caesiumclt is not built (python -c 'import __graft_entry__ as g; g.build()')"
+    E.run_cli_over_a_gif(PRODUCT_CLI, tmp_path)
