@@ -36,7 +36,7 @@ class PngTiming(C.Structure):
 
 class GifTiming(C.Structure):
     _fields_ = [("total_ms", C.c_float), ("kernel_ms", C.c_float * 8), ("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("n_files", C.c_uint32), ("n_frames", C.c_uint32),
-                ("n_failed", C.c_uint32), ("n_passed_palette", C.c_uint32), ("n_not_smaller", C.c_uint32), ("chunk_pixels", C.c_uint32)]
+                ("n_failed", C.c_uint32), ("n_passed_palette", C.c_uint32), ("n_not_smaller", C.c_uint32), ("chunk_pixels", C.c_uint32), ("lossy_distance", C.c_uint32)]
 
 
 class CaesiumError(RuntimeError):
@@ -56,7 +56,7 @@ EXPORTS = ["cs_default_parameters", "cs_compress_in_memory", "cs_compress_to_siz
            "csp_batch_trials", "csp_batch_read_scores", "csp_batch_chunk_bits", "csh_batch_create_webp", "cs_batch_convert",
            "cswd_batch_create", "cswd_batch_run", "cswd_batch_pixels", "cswd_batch_read_pixels", "cswd_batch_alpha", "cswd_batch_read_rgba", "cswd_batch_destroy", "cswd_batch_frames", "cswd_batch_read_canvas", "cswd_batch_encode_anim", "cswd_rgba_join", "cswd_rgba_destroy", "csh_batch_create_webp_from_pixels", "csh_batch_create_from_pixels_rgb", "csl_encode_pixels", "csl_attach_alpha"]
 # the GIF batch's entry points (the csg_ prefix): a list of their own, beside the one above
-GIF_EXPORTS = ["csg_kernel_name", "csg_batch_create", "csg_batch_run", "csg_batch_fetch", "csg_batch_destroy", "csg_batch_frames", "csg_batch_read_indices", "csg_batch_read_canvas"]
+GIF_EXPORTS = ["csg_kernel_name", "csg_batch_create", "csg_batch_run", "csg_batch_fetch", "csg_batch_destroy", "csg_batch_frames", "csg_batch_read_indices", "csg_batch_read_canvas", "csg_batch_create_lossy", "csg_batch_read_near"]
 
 
 def _declare(L):
@@ -132,6 +132,8 @@ def _declare(L):
     L.csg_batch_frames.argtypes = [C.c_void_p, C.c_size_t, P(C.c_uint32), P(C.c_uint32), P(C.c_uint32)]
     L.csg_batch_read_indices.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
     L.csg_batch_read_canvas.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
+    L.csg_batch_create_lossy.argtypes = [P(CByteArray), C.c_size_t, P(CCSParameters), C.c_int, P(C.c_void_p)]
+    L.csg_batch_read_near.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]
     return L
 
 
@@ -324,9 +326,10 @@ class PngBatch:
 
 
 class GifBatch:
-    """csg_batch: a group of GIF files, decoded, composed and coded again on the device (the route CSH_GIF=device selects)."""
+    """csg_batch: a group of GIF files, decoded, composed and coded again on the device (the route CSH_GIF=device selects; lossy: the one CSH_GIF=lossy selects,
+    the bounded-error coder at params.gif_quality)."""
 
-    def __init__(self, api, blobs, params, device=0):
+    def __init__(self, api, blobs, params, device=0, lossy=False):
         self.api = api
         L = api.L
         self.n = len(blobs)
@@ -336,7 +339,7 @@ class GifBatch:
             self._in[i].data = C.cast(buf, C.POINTER(C.c_uint8))
             self._in[i].length = len(blobs[i])
         self.h = C.c_void_p()
-        rc = L.csg_batch_create(self._in, self.n, C.byref(params), device, C.byref(self.h))
+        rc = (L.csg_batch_create_lossy if lossy else L.csg_batch_create)(self._in, self.n, C.byref(params), device, C.byref(self.h))
         if rc:
             raise CaesiumError(rc, L.csh_last_error().decode())
 
@@ -384,6 +387,15 @@ class GifBatch:
         if rc:
             raise CaesiumError(rc, self.api.L.csh_last_error().decode())
         return a
+
+    def near(self, file, frame):
+        """-> (cand [256][64], count [256]): the candidate rows of the table frame `frame` uses, as the lossy coder reads them"""
+        import numpy as np
+        cand, count = np.empty((256, 64), dtype=np.uint8), np.empty(256, dtype=np.uint8)
+        rc = self.api.L.csg_batch_read_near(self.h, file, frame, cand.ctypes.data, count.ctypes.data)
+        if rc:
+            raise CaesiumError(rc, self.api.L.csh_last_error().decode())
+        return cand, count
 
     def close(self):
         if getattr(self, "h", None):
@@ -534,8 +546,8 @@ class CaesiumHip:
         finally:
             L.cswd_batch_destroy(h)
 
-    def gif_batch(self, blobs, params=None, device=0):
-        return GifBatch(self, blobs, params or default_parameters(), device)
+    def gif_batch(self, blobs, params=None, device=0, lossy=False):
+        return GifBatch(self, blobs, params or default_parameters(), device, lossy)
 
     def gif_kernel_names(self):
         return [self.L.csg_kernel_name(i).decode() for i in range(8)]

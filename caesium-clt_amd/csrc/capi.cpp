@@ -57,7 +57,8 @@ static uint64_t declared_pixels(const uint8_t *d, size_t n) {
 // that holds such files (configs[4], /root/reference/src/compressor.rs:774 hands the engine a .tif) then completes without error lines; the
 // caller's overwrite / min-savings policy sees equal sizes and acts on that.  A resize or a conversion of such a file is still refused.
 // A GIF file leaves this path under CSH_GIF=device (read on every call; unset, empty or "pass": here as before): route::gif_compress optimises it, pixel-exact
-// (DESIGN.md 8.3); its resize is still answered here, and any other value of the variable fails the call's GIF files with CS_ERR_UNSUPPORTED.
+// (DESIGN.md 8.3), and under CSH_GIF=lossy with the bounded-error coder at gif_quality; its resize is still answered here, and any other value of the variable
+// fails the call's GIF files with CS_ERR_UNSUPPORTED.
 static CCSResult passthrough(const CByteArray &in, const CCSParameters *p, CByteArray *out) {
     out->data = nullptr; out->length = 0;
     if (p->width || p->height) return make_result(CS_ERR_UNSUPPORTED, "resizing a GIF / TIFF file has no path in this build (the file itself is passed through without a size)");
@@ -66,19 +67,20 @@ static CCSResult passthrough(const CByteArray &in, const CCSParameters *p, CByte
     memcpy(out->data, in.data, in.length); out->length = in.length;
     return make_result(0, nullptr);
 }
-// CSH_GIF: 0 pass the file through, 1 the device route, -1 a value that names neither
+// CSH_GIF: 0 pass the file through, 1 the device route, 2 the device route with the lossy coder at gif_quality, -1 a value that names none of them
 static int gif_mode() {
     const char *e = getenv("CSH_GIF");
     if (!e || !*e || !strcmp(e, "pass")) return 0;
-    return !strcmp(e, "device") ? 1 : -1;
+    return !strcmp(e, "device") ? 1 : !strcmp(e, "lossy") ? 2 : -1;
 }
 // the files of a compress call by the row that takes them; a TIFF file, and a GIF file outside CSH_GIF=device, is answered on the spot, by pass(i) -- or by
 // refuse(i) under a value of CSH_GIF that means nothing
-struct Rows { std::vector<size_t> png, webp, gif, other; bool any_pass = false; };
+struct Rows { std::vector<size_t> png, webp, gif, other; bool any_pass = false, gif_lossy = false; };
 template <class Pass, class Refuse>
 static Rows sort_rows(const CByteArray *inputs, size_t count, const CCSParameters *p, Pass pass, Refuse refuse) {
     Rows r;
     const int gif = gif_mode();
+    r.gif_lossy = gif == 2;
     for (size_t i = 0; i < count; i++) {
         const int t = sniff(inputs[i].data, inputs[i].length);
         if (t == CS_TYPE_GIF && gif < 0) { refuse(i); r.any_pass = true; }
@@ -90,7 +92,7 @@ static Rows sort_rows(const CByteArray *inputs, size_t count, const CCSParameter
 }
 
 // A caller may pass no results array: the routes always write one, so such a call gets an array of its own here, released when the call returns
-static const char *const BAD_CSH_GIF = "CSH_GIF names no GIF path (unset, empty or \"pass\": the file is passed through; \"device\": the pixel-exact optimiser)";
+static const char *const BAD_CSH_GIF = "CSH_GIF names no GIF path (unset, empty or \"pass\": the file is passed through; \"device\": the pixel-exact optimiser; \"lossy\": the same with the bounded-error coder at gif_quality)";
 
 struct Results {
     std::vector<CCSResult> own;
@@ -164,7 +166,7 @@ int cs_batch_compress(const CByteArray *inputs, size_t count, const CCSParameter
     auto run = [&](const std::vector<size_t> &idx, int kind) {
         failed += route::for_subset(inputs, idx, outputs, results, [&](const CByteArray *in, size_t n, CByteArray *out, CCSResult *res) {
             return kind == 1 ? route::png_compress(in, n, p, device, out, res, false) : kind == 2 ? route::webp_inputs(in, n, p, CS_TYPE_WEBP, device, out, res) :
-                   kind == 3 ? route::gif_compress(in, n, p, device, out, res) : route::jpeg_compress(in, n, p, device, out, res);
+                   kind == 3 ? route::gif_compress(in, n, p, device, out, res, r.gif_lossy) : route::jpeg_compress(in, n, p, device, out, res);
         });
     };
     // the rows side by side (each batch keeps to its own stream; their outputs are disjoint): a tree of all three kinds waits for its slowest row only
@@ -199,9 +201,10 @@ int cs_batch_compress_to_size(const CByteArray *inputs, size_t count, CCSParamet
         if (!results[i].success) failed++;
         hold_to_target(i, "the file is passed through as it is (GIF / TIFF have no device path) and is larger than the target size");
     }, [&](size_t i) { outputs[i].data = nullptr; outputs[i].length = 0; results[i] = make_result(CS_ERR_UNSUPPORTED, BAD_CSH_GIF); failed++; });
-    // a GIF file under CSH_GIF=device: one run of its route (the optimiser is pixel-exact: there is no quality to walk), then the same rule
-    failed += route::for_subset(inputs, rows.gif, outputs, results, [&](const CByteArray *in, size_t n, CByteArray *out, CCSResult *res) { return route::gif_compress(in, n, p, device, out, res); });
-    for (size_t i : rows.gif) hold_to_target(i, "the GIF optimiser is pixel-exact and has no quality to walk: its one result is larger than the target size");
+    // a GIF file under CSH_GIF=device / lossy: one run of its route (the optimiser is pixel-exact, and the lossy coder runs at the quality given: no quality is walked), then the same rule
+    failed += route::for_subset(inputs, rows.gif, outputs, results, [&](const CByteArray *in, size_t n, CByteArray *out, CCSResult *res) { return route::gif_compress(in, n, p, device, out, res, rows.gif_lossy); });
+    for (size_t i : rows.gif) hold_to_target(i, rows.gif_lossy ? "the GIF route runs once, at the quality given, and walks no quality: its one result is larger than the target size"
+                                                               : "the GIF optimiser is pixel-exact and has no quality to walk: its one result is larger than the target size");
     if (rows.png.empty() && rows.webp.empty() && rows.gif.empty() && !rows.any_pass) return route::jpeg_compress_to_size(inputs, count, p, max_output_size, return_smallest, device, outputs, results);
     // the JPEG walk leaves its last quality in the caller's parameters, as the reference's &mut does
     failed += route::for_subset(inputs, rows.other, outputs, results, [&](const CByteArray *in, size_t n, CByteArray *out, CCSResult *res) {

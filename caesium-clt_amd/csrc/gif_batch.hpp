@@ -46,11 +46,13 @@ struct csg_batch {
     std::vector<csg::GifFrame> frames;
     std::vector<uint32_t> frame_file;
     std::vector<uint8_t> out;             // the device's output pool, read back
-    csh::DevBuf<uint8_t> d_data, d_idx, d_canon;
-    csh::DevBuf<uint32_t> d_tables;
+    csh::DevBuf<uint8_t> d_data, d_idx, d_canon, d_cand, d_cand_n;   // (the candidate rows and their lengths: a lossy batch with a distance alone)
+    csh::DevBuf<uint32_t> d_tables, d_table_n;
     csh::DevBuf<csg::GifFrame> d_frames;
     csh::DevBuf<csg::GifFile> d_files;
     uint32_t chunk_pixels = 16384;
+    uint32_t distance = 0;                // D of the lossy coder; 0: the exact coder
+    uint32_t ntables = 0;                 // tables d_cand holds rows for (0 without a distance)
     csg_timing timing;
     ~csg_batch() { if (have_stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); } }
 };

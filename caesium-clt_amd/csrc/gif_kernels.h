@@ -38,6 +38,12 @@ void launch_gif_lzw_decode(hipStream_t st, const GifFrame *frames, uint32_t nfra
 void launch_gif_anim(hipStream_t st, int mode, const GifFile *files, uint32_t nfiles, uint64_t max_px, const GifFrame *frames, const uint8_t *indices, const uint32_t *tables, const uint8_t *canon,
                      uint32_t *stats, uint32_t *file_flags, uint8_t *pool, uint32_t target);
 void launch_gif_lzw_encode(hipStream_t st, const GifFrame *frames, const GifChunk *chunks, uint32_t nchunks, const uint8_t *pack, uint8_t *cbuf, uint32_t *cbits, uint32_t chunk_px);
+// the lossy coder (CSH_GIF=lossy, D > 0).  A table's candidate rows: cand[(table * 256 + b) * 64 + l], l < count[table * 256 + b], is b itself (l = 0), then the
+// canonical indices below the table's n whose colour lies within D of b's, by (distance squared, index), 63 at most
+enum : uint32_t { GIF_NEAR_ROW = 64 };
+void launch_gif_near(hipStream_t st, const uint32_t *tables, const uint8_t *canon, const uint32_t *table_n, uint32_t ntables, uint32_t dist, uint8_t *cand, uint8_t *count);
+void launch_gif_lzw_encode_lossy(hipStream_t st, const GifFrame *frames, const GifChunk *chunks, uint32_t nchunks, const uint8_t *pack, const uint8_t *cand, const uint8_t *count, uint8_t *cbuf,
+                                 uint32_t *cbits, uint32_t chunk_px);
 void launch_gif_layout(hipStream_t st, const GifFile *files, uint32_t nfiles, const GifFrame *frames, const uint32_t *cbits, uint64_t *cstart, GifPlace *place, uint64_t *file_bytes);
 void launch_gif_frame_head(hipStream_t st, const GifFile *files, const GifFrame *frames, const uint32_t *frame_file, uint32_t nframes, const uint8_t *heads, const GifPlace *place, uint8_t *out);
 void launch_gif_merge(hipStream_t st, const GifFile *files, const GifFrame *frames, const uint32_t *frame_file, const GifChunk *chunks, uint32_t nchunks, const uint8_t *cbuf, const uint32_t *cbits,

@@ -11,6 +11,8 @@
 // chunk starts from (the last chunk: with the end code), so chunks do not depend on one another.  The dictionary is an open-addressed hash table of 8192 words
 // in LDS; the wave probes 64 consecutive slots with one read and two ballots.  k_gif_layout scans the chunks' bit lengths and places the frames in their files,
 // k_gif_merge shifts the chunks' bits together into 255-byte sub-blocks, k_gif_frame_head writes what stands around them.
+// Under CSH_GIF=lossy (a distance D > 0) k_gif_near lists every table colour's neighbours within D and k_gif_lzw_encode_lossy codes the chunks instead: the
+// match goes on with a neighbour of the next pixel's colour when the dictionary holds one.
 #include "gif_kernels.h"
 #include "wave.h"
 
@@ -219,6 +221,144 @@ __global__ void __launch_bounds__(CSP_WAVE_THREADS) k_gif_lzw_encode(const GifFr
 void launch_gif_lzw_encode(hipStream_t st, const GifFrame *frames, const GifChunk *chunks, uint32_t nchunks, const uint8_t *pack, uint8_t *cbuf, uint32_t *cbits, uint32_t chunk_px) {
     if (!nchunks) return;
     CSH_LAUNCH(k_gif_lzw_encode, dim3(nchunks), dim3(CSP_WAVE_THREADS), st, frames, chunks, pack, cbuf, cbits, chunk_px);
+}
+
+// ------------------------------------------------------------------------------------------------ the lossy coder (CSH_GIF=lossy, D > 0)
+// A colour table's candidate rows.  One wave per (table, index b); lane l holds the entries c = l, 64 + l, 128 + l, 192 + l as keys distance^2 << 8 | c (26 bits:
+// 3 * 255^2 < 2^18).  An entry that is b itself, stands at or behind the table's n, repeats a lower entry's colour or lies further than D from b has no key; a row
+// whose b is such an entry holds b alone.  A key's place in the row is the number of smaller keys -- the keys carry the index, so no two are equal -- and the first
+// 63 are kept behind b.  The rows were zeroed by the host.
+enum : uint32_t { NEAR_NONE = 0xFFFFFFFFu };
+__device__ __forceinline__ static uint32_t rgb_dist2(uint32_t a, uint32_t b) {
+    const int32_t dr = int32_t(a & 255u) - int32_t(b & 255u), dg = int32_t((a >> 8) & 255u) - int32_t((b >> 8) & 255u), db = int32_t((a >> 16) & 255u) - int32_t((b >> 16) & 255u);
+    return uint32_t(dr * dr + dg * dg + db * db);
+}
+__global__ void __launch_bounds__(CSP_WAVE_THREADS) k_gif_near(const uint32_t *tables, const uint8_t *canon, const uint32_t *table_n, uint32_t dist, uint8_t *cand, uint8_t *count) {
+    CSH_SHARED uint32_t s_key[256];
+    const uint32_t t = blockIdx.x >> 8, b = blockIdx.x & 255u, n = table_n[t];
+    const uint32_t *tb = tables + size_t(t) * 256u;
+    const uint8_t *cn = canon + size_t(t) * 256u;
+    uint8_t *row = cand + (size_t(t) * 256u + b) * GIF_NEAR_ROW;
+    const bool listed = b < n && cn[b] == b;
+    const uint32_t cb = tb[b], d2max = dist * dist;
+    LV<uint32_t> key[4];
+    LFOR(l) {
+        CSH_UNROLL
+        for (uint32_t q = 0; q < 4; q++) {
+            const uint32_t c = q * 64u + uint32_t(l), d2 = rgb_dist2(tb[c], cb);
+            key[q][l] = (listed && c != b && c < n && cn[c] == c && d2 <= d2max) ? ((d2 << 8) | c) : uint32_t(NEAR_NONE);
+            s_key[c] = key[q][l];
+        }
+    }
+    CSP_WAVE_SYNC();
+    uint32_t total = 0;
+    for (uint32_t q = 0; q < 4; q++) total += csh::popc64(lballot([&](int l) { return key[q][l] != NEAR_NONE; }));
+    LFOR(l) {
+        uint32_t rank[4] = {0, 0, 0, 0};
+        for (uint32_t j = 0; j < 256u; j++) {
+            const uint32_t k = s_key[j];   // (no key is below a smaller one: NEAR_NONE is the largest word)
+            CSH_UNROLL
+            for (uint32_t q = 0; q < 4; q++) rank[q] += k < key[q][l] ? 1u : 0u;
+        }
+        CSH_UNROLL
+        for (uint32_t q = 0; q < 4; q++) if (key[q][l] != NEAR_NONE && rank[q] < GIF_NEAR_ROW - 1u) row[1u + rank[q]] = uint8_t(key[q][l] & 255u);
+        if (l == 0) { row[0] = uint8_t(b); count[size_t(t) * 256u + b] = uint8_t(1u + (total < GIF_NEAR_ROW - 1u ? total : GIF_NEAR_ROW - 1u)); }
+    }
+}
+void launch_gif_near(hipStream_t st, const uint32_t *tables, const uint8_t *canon, const uint32_t *table_n, uint32_t ntables, uint32_t dist, uint8_t *cand, uint8_t *count) {
+    for (uint32_t t0 = 0; t0 < ntables; t0 += 1u << 20) {   // (a grid's x stays below 2^31)
+        const uint32_t nt = ntables - t0 < (1u << 20) ? ntables - t0 : (1u << 20);
+        CSH_LAUNCH(k_gif_near, dim3(nt * 256u), dim3(CSP_WAVE_THREADS), st, tables + size_t(t0) * 256u, canon + size_t(t0) * 256u, table_n + t0, dist, cand + size_t(t0) * 256u * GIF_NEAR_ROW, count + size_t(t0) * 256u);
+    }
+}
+
+// One wave per chunk, as k_gif_lzw_encode, over the same hash words; the wave's lanes take the candidates of the next pixel b instead of 64 neighbouring slots.
+// Lane l looks (cur, cand(b)[l]) up along its own linear-probe chain -- the exact coder fills the first empty slot from the hash on, so a chain ends on the key or
+// on an empty slot --, one ballot finds the first candidate the dictionary holds, and the match goes on with it: the decoder shows that colour, which lies within
+// D of b's.  A candidate equal to the frame's transparent index is skipped, and a transparent b (or one behind the table) has no candidate but itself: alpha is
+// never touched.  With no hit the code is sent and (cur, b), the exact pixel, goes where lane 0's chain ended.  The coder sends no more codes than the exact one
+// would for the pixels it shows, so gif_chunk_cap bounds the chunk.  LDS: the table (32 KB) and the frame's rows (16 KB + 256 B): three workgroups a CU.
+__global__ void __launch_bounds__(CSP_WAVE_THREADS) k_gif_lzw_encode_lossy(const GifFrame *frames, const GifChunk *chunks, const uint8_t *pack, const uint8_t *cand, const uint8_t *count, uint8_t *cbuf, uint32_t *cbits,
+                                                                            uint32_t chunk_px) {
+    CSH_SHARED uint32_t s_tab[ENC_SLOTS];
+    CSH_SHARED uint32_t s_rows[256u * GIF_NEAR_ROW / 4u];
+    CSH_SHARED uint32_t s_count[256u / 4u];
+    const GifChunk ck = chunks[blockIdx.x];
+    const GifFrame f = frames[ck.frame];
+    const uint32_t npx = f.ow * f.oh, p0 = ck.index * chunk_px, n = npx - p0 < chunk_px ? npx - p0 : chunk_px;
+    const uint8_t *px = pack + f.out_off + p0;
+    uint32_t *dst = reinterpret_cast<uint32_t *>(cbuf + ck.buf_off);
+    const uint32_t clear = 1u << f.omcs;
+    uint32_t width = f.omcs + 1u, next = clear + 2u, nb = 0, words = 0;
+    uint64_t acc = 0;
+    auto emit = [&](uint32_t code) {
+        acc |= uint64_t(code) << nb; nb += width;
+        if (nb >= 32u) { LFOR(l) if (l == 0) dst[words] = uint32_t(acc); words++; acc >>= 32; nb -= 32u; }
+    };
+    auto wipe = [&]() {
+        CSP_WAVE_SYNC();
+        LFOR(l) for (uint32_t s = uint32_t(l); s < ENC_SLOTS; s += 64u) s_tab[s] = ENC_EMPTY;
+        CSP_WAVE_SYNC();
+    };
+    auto after_code = [&](uint32_t slot, uint32_t key, bool insert) {
+        if (next < 4096u) {
+            if (insert) { LFOR(l) if (l == 0) s_tab[slot] = (key << 12) | next; CSP_WAVE_SYNC(); }
+            next++;
+            if (next > (1u << width) && width < 12u) width++;
+        } else { emit(clear); if (insert) wipe(); width = f.omcs + 1u; next = clear + 2u; }
+    };
+    {   // the rows of the frame's table (the pools are word-aligned: a table's rows are 16 KB, its counts 256 bytes)
+        const uint32_t *gr = reinterpret_cast<const uint32_t *>(cand + size_t(f.pal) * 256u * GIF_NEAR_ROW), *gc = reinterpret_cast<const uint32_t *>(count + size_t(f.pal) * 256u);
+        LFOR(l) {
+            for (uint32_t i = uint32_t(l); i < 256u * GIF_NEAR_ROW / 4u; i += 64u) s_rows[i] = gr[i];
+            s_count[l] = gc[l];
+        }
+    }
+    const uint8_t *rows = reinterpret_cast<const uint8_t *>(s_rows), *counts = reinterpret_cast<const uint8_t *>(s_count);
+    wipe();
+    if (ck.index == 0) emit(clear);
+    uint32_t cur = 0;
+    bool have = false;
+    for (uint32_t base = 0; base < n; base += 64u) {
+        LV<uint32_t> pv;
+        LFOR(l) pv[l] = base + uint32_t(l) < n ? uint32_t(px[base + uint32_t(l)]) : 0u;
+        const uint32_t cnt = n - base < 64u ? n - base : 64u;
+        for (uint32_t j = 0; j < cnt; j++) {
+            const uint32_t b = lget(pv, j);
+            if (!have) { cur = b; have = true; continue; }
+            const uint32_t nc = b == f.transparent ? 1u : uint32_t(counts[b]);
+            LV<uint32_t> found, slot;
+            LFOR(l) {
+                const uint32_t c = rows[b * GIF_NEAR_ROW + uint32_t(l)];
+                found[l] = ENC_EMPTY; slot[l] = 0u;
+                if (uint32_t(l) < nc && (l == 0 || c != f.transparent)) {
+                    const uint32_t key = (cur << 8) | c;
+                    uint32_t h = (key * 2654435761u) >> 19, sv;
+                    for (;;) {   // the table is at most half full: an empty slot ends the chain
+                        sv = s_tab[h & (ENC_SLOTS - 1u)];
+                        if (sv == ENC_EMPTY || (sv >> 12) == key) break;
+                        h++;
+                    }
+                    found[l] = sv; slot[l] = h & (ENC_SLOTS - 1u);
+                }
+            }
+            const uint64_t hit = lballot([&](int l) { return found[l] != ENC_EMPTY; });
+            if (hit) { cur = lget(found, uint32_t(__ffsll((unsigned long long)hit)) - 1u) & 0xFFFu; continue; }
+            emit(cur);
+            after_code(lget(slot, 0u), (cur << 8) | b, true);
+            cur = b;
+        }
+    }
+    emit(cur);
+    after_code(0, 0, false);
+    emit(ck.index + 1u == f.nchunks ? clear + 1u : clear);
+    const uint32_t bits = words * 32u + nb;
+    LFOR(l) if (l == 0) { if (nb) dst[words] = uint32_t(acc); cbits[blockIdx.x] = bits; }
+}
+void launch_gif_lzw_encode_lossy(hipStream_t st, const GifFrame *frames, const GifChunk *chunks, uint32_t nchunks, const uint8_t *pack, const uint8_t *cand, const uint8_t *count, uint8_t *cbuf,
+                                 uint32_t *cbits, uint32_t chunk_px) {
+    if (!nchunks) return;
+    CSH_LAUNCH(k_gif_lzw_encode_lossy, dim3(nchunks), dim3(CSP_WAVE_THREADS), st, frames, chunks, pack, cand, count, cbuf, cbits, chunk_px);
 }
 
 // one lane per file: the chunks' bit offsets inside their frame, the frames' places inside their file, the file's size

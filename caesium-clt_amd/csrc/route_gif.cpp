@@ -1,4 +1,4 @@
-// route_gif.cpp -- GIF inputs under CSH_GIF=device: the csg_batch (container walk on the host; LZW decode, canvas walk, LZW coder and the
+// route_gif.cpp -- GIF inputs under CSH_GIF=device / lossy: the csg_batch (container walk on the host; LZW decode, canvas walk, LZW coder and the
 // assembly of the files on the device) and the route that feeds it in groups.  The output renders what the input renders, canvas for canvas: frames shrink to what
 // changed, unchanged pixels are written transparent, the LZW streams are coded afresh; a file that did not get smaller comes back as it is.
 #include <algorithm>
@@ -11,8 +11,8 @@ using namespace csh;
 using namespace csg;
 
 namespace {
-enum { K_DECODE, K_STATS, K_PACK, K_ENCODE, K_LAYOUT, K_HEAD, K_MERGE };
-const char *const KERNEL_NAMES[CSG_NKERNELS] = {"gif_lzw_decode", "gif_anim_stats", "gif_anim_pack", "gif_lzw_encode", "gif_layout", "gif_frame_head", "gif_merge", ""};
+enum { K_DECODE, K_STATS, K_PACK, K_ENCODE, K_LAYOUT, K_HEAD, K_MERGE, K_NEAR };   // (K_ENCODE times whichever coder the batch runs: it runs one)
+const char *const KERNEL_NAMES[CSG_NKERNELS] = {"gif_lzw_decode", "gif_anim_stats", "gif_anim_pack", "gif_lzw_encode", "gif_layout", "gif_frame_head", "gif_merge", "gif_near"};
 
 uint32_t chunk_pixels_from_env() {
     const char *e = getenv("CSH_GIF_CHUNK");
@@ -34,11 +34,12 @@ Box unite(const Box &a, const Box &b) {
 
 extern "C" const char *csg_kernel_name(int slot) { return slot >= 0 && slot < CSG_NKERNELS ? KERNEL_NAMES[slot] : ""; }
 
-extern "C" int csg_batch_create(const CByteArray *inputs, size_t count, const CCSParameters *p, int device, csg_batch **out) {
+// distance 0: the exact coder
+static int batch_create(const CByteArray *inputs, size_t count, const CCSParameters *p, int device, uint32_t distance, csg_batch **out) {
     *out = nullptr;
     if (hipSetDevice(device) != hipSuccess) { csh_set_error("hipSetDevice failed"); return CS_ERR_NO_DEVICE; }
     csg_batch *b = new csg_batch;
-    b->device = device; b->inputs = inputs; b->keep_metadata = p->keep_metadata; b->chunk_pixels = chunk_pixels_from_env();   // (gif_quality is read by nobody: the route is pixel-exact)
+    b->device = device; b->inputs = inputs; b->keep_metadata = p->keep_metadata; b->chunk_pixels = chunk_pixels_from_env(); b->distance = distance;
     memset(&b->timing, 0, sizeof b->timing);
     if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) { delete b; csh_set_error("hipStreamCreate failed"); return CS_ERR_NO_DEVICE; }
     b->have_stream = true;
@@ -63,6 +64,14 @@ extern "C" int csg_batch_create(const CByteArray *inputs, size_t count, const CC
     return 0;
 }
 
+extern "C" int csg_batch_create(const CByteArray *inputs, size_t count, const CCSParameters *p, int device, csg_batch **out) {
+    return batch_create(inputs, count, p, device, 0, out);   // (gif_quality is not read: this batch is pixel-exact)
+}
+// D = 100 - quality, the quality held to 1..100 (0 counts as 1, as in libcaesium; --lossless sets 100)
+extern "C" int csg_batch_create_lossy(const CByteArray *inputs, size_t count, const CCSParameters *p, int device, csg_batch **out) {
+    return batch_create(inputs, count, p, device, 100u - std::min(100u, std::max(1u, p->gif_quality)), out);
+}
+
 extern "C" void csg_batch_destroy(csg_batch *b) { delete b; }
 
 extern "C" int csg_batch_run(csg_batch *b, csg_timing *t) {
@@ -70,7 +79,7 @@ extern "C" int csg_batch_run(csg_batch *b, csg_timing *t) {
     const hipStream_t st = b->stream;
     csg_timing &T = b->timing;
     memset(&T, 0, sizeof T);
-    T.chunk_pixels = b->chunk_pixels; T.n_files = uint32_t(b->items.size());
+    T.chunk_pixels = b->chunk_pixels; T.lossy_distance = b->distance; T.n_files = uint32_t(b->items.size());
     hipEvent_t ev[2 * CSG_NKERNELS + 2] = {};
     bool launched[CSG_NKERNELS] = {false};
     auto timed = [&](int slot, auto fn) { (void)hipEventRecord(ev[2 * slot], st); fn(); (void)hipEventRecord(ev[2 * slot + 1], st); launched[slot] = true; };
@@ -81,12 +90,12 @@ extern "C" int csg_batch_run(csg_batch *b, csg_timing *t) {
     // ---- the frames, their colour tables and their streams
     std::vector<GifFrame> &frames = b->frames;
     frames.clear(); b->frame_file.clear();
-    std::vector<uint32_t> tables;
+    std::vector<uint32_t> tables, table_n;   // 256 words a table, and how many of them the file gave
     std::vector<uint8_t> canon, data;
     uint64_t idx_bytes = 0, max_px = 0;
     auto add_table = [&](const uint8_t *rgb, size_t len) {
         const uint32_t at = uint32_t(tables.size() / 256), n = uint32_t(len / 3);
-        tables.resize(tables.size() + 256, 0xFF000000u); canon.resize(canon.size() + 256);
+        tables.resize(tables.size() + 256, 0xFF000000u); canon.resize(canon.size() + 256); table_n.push_back(n);
         uint32_t *tb = &tables[size_t(at) * 256];
         for (uint32_t i = 0; i < n; i++) tb[i] = uint32_t(rgb[3 * i]) | (uint32_t(rgb[3 * i + 1]) << 8) | (uint32_t(rgb[3 * i + 2]) << 16) | 0xFF000000u;
         for (uint32_t i = 0; i < 256; i++) { uint32_t j = 0; while (j < std::min(i, n) && tb[j] != tb[i]) j++; canon[size_t(at) * 256 + i] = uint8_t(j < std::min(i, n) ? j : i); }   // the lowest index of the same colour
@@ -196,8 +205,17 @@ extern "C" int csg_batch_run(csg_batch *b, csg_timing *t) {
     if (b->d_frames.upload(frames, st) || d_coded.upload(coded, st) || d_chunks.upload(chunks, st) || d_heads.upload(heads, st) || d_pack.alloc(size_t(pack_bytes) + 64) || d_cbuf.alloc(size_t(cbuf_bytes) + 64) ||
         d_cbits.alloc(nchunks) || d_cstart.alloc(nchunks) || d_place.alloc(nframes) || d_file_bytes.alloc(nfiles) || d_out.alloc(size_t(out_bytes) + 64))
         return done(CS_ERR_NO_DEVICE);
+    const bool lossy = b->distance > 0;   // else the launches are the exact route's
+    b->ntables = lossy ? uint32_t(table_n.size()) : 0u;
+    if (lossy) {
+        if (b->d_table_n.upload(table_n, st) || b->d_cand.alloc(size_t(b->ntables) * 256 * GIF_NEAR_ROW) || b->d_cand.zero(st) || b->d_cand_n.alloc(size_t(b->ntables) * 256)) return done(CS_ERR_NO_DEVICE);
+        timed(K_NEAR, [&] { launch_gif_near(st, b->d_tables.p, b->d_canon.p, b->d_table_n.p, b->ntables, b->distance, b->d_cand.p, b->d_cand_n.p); });
+    }
     timed(K_PACK, [&] { launch_gif_anim(st, GIF_WALK_PACK, d_coded.p, nfiles, max_px, b->d_frames.p, b->d_idx.p, b->d_tables.p, b->d_canon.p, d_stats.p, d_flags.p, d_pack.p, 0); });
-    timed(K_ENCODE, [&] { launch_gif_lzw_encode(st, b->d_frames.p, d_chunks.p, nchunks, d_pack.p, d_cbuf.p, d_cbits.p, b->chunk_pixels); });
+    timed(K_ENCODE, [&] {
+        if (lossy) launch_gif_lzw_encode_lossy(st, b->d_frames.p, d_chunks.p, nchunks, d_pack.p, b->d_cand.p, b->d_cand_n.p, d_cbuf.p, d_cbits.p, b->chunk_pixels);
+        else launch_gif_lzw_encode(st, b->d_frames.p, d_chunks.p, nchunks, d_pack.p, d_cbuf.p, d_cbits.p, b->chunk_pixels);
+    });
     timed(K_LAYOUT, [&] { launch_gif_layout(st, d_coded.p, nfiles, b->d_frames.p, d_cbits.p, d_cstart.p, d_place.p, d_file_bytes.p); });
     timed(K_HEAD, [&] { launch_gif_frame_head(st, d_coded.p, b->d_frames.p, d_frame_file.p, nframes, d_heads.p, d_place.p, d_out.p); });
     timed(K_MERGE, [&] { launch_gif_merge(st, d_coded.p, b->d_frames.p, d_frame_file.p, d_chunks.p, nchunks, d_cbuf.p, d_cbits.p, d_cstart.p, d_place.p, d_out.p); });
@@ -280,16 +298,33 @@ extern "C" int csg_batch_read_canvas(csg_batch *b, size_t file, uint32_t frame, 
     return 0;
 }
 
+extern "C" int csg_batch_read_near(csg_batch *b, size_t file, uint32_t frame, uint8_t *cand, uint8_t *count) {
+    const csg_batch::Item *it = tap_item(b, file, "csg_batch_read_near");
+    if (!it) return -1;
+    if (it->code) return it->code;
+    if (!b->ran || it->file < 0 || frame >= b->files[size_t(it->file)].nframes) { csh_set_error("csg_batch_read_near: batch not run / a file that is passed through / no such frame"); return -1; }
+    const uint32_t pal = b->frames[b->files[size_t(it->file)].first + frame].pal;
+    if (!b->distance || pal >= b->ntables) {   // no distance (or nothing was coded): every index stands alone
+        memset(cand, 0, 256 * GIF_NEAR_ROW);
+        for (uint32_t i = 0; i < 256; i++) { cand[i * GIF_NEAR_ROW] = uint8_t(i); count[i] = 1; }
+        return 0;
+    }
+    if (hipSetDevice(b->device) != hipSuccess) { csh_set_error("hipSetDevice failed"); return CS_ERR_NO_DEVICE; }
+    if (csh_copy_wait(cand, b->d_cand.p + size_t(pal) * 256 * GIF_NEAR_ROW, 256 * GIF_NEAR_ROW, hipMemcpyDeviceToHost, b->stream) != hipSuccess ||
+        csh_copy_wait(count, b->d_cand_n.p + size_t(pal) * 256, 256, hipMemcpyDeviceToHost, b->stream) != hipSuccess) { csh_set_error("csg_batch_read_near: copy failed"); return CS_ERR_NO_DEVICE; }
+    return 0;
+}
+
 namespace route {
 
 // GIF -> GIF: groups of at most 1024 files, sized by what they hold on the device -- per pixel of every frame the decoded index, the output index, a byte and a
 // half of chunk buffer and as much of output, beside the file itself
-int gif_compress(const CByteArray *inputs, size_t count, const CCSParameters *p, int device, CByteArray *outputs, CCSResult *results) {
+int gif_compress(const CByteArray *inputs, size_t count, const CCSParameters *p, int device, CByteArray *outputs, CCSResult *results, bool lossy) {
     int failed_total = 0;
     for (size_t g0 = 0, n = 0; g0 < count; g0 += n) {
         n = group_extent(inputs + g0, count - g0, 1024, uint64_t(2) << 30, uint64_t(96) << 30, [](const CByteArray &f) { return uint64_t(1 << 20) + 2 * uint64_t(f.length) + csg_declared_pixels(f.data, f.length) * 6; });
         csg_batch *b = nullptr;
-        int rc = csg_batch_create(inputs + g0, n, p, device, &b);
+        int rc = lossy ? csg_batch_create_lossy(inputs + g0, n, p, device, &b) : csg_batch_create(inputs + g0, n, p, device, &b);
         if (rc == 0) rc = csg_batch_run(b, nullptr);
         if (rc != 0) {
             for (size_t i = 0; i < n; i++) { outputs[g0 + i].data = nullptr; outputs[g0 + i].length = 0; results[g0 + i] = make_result(rc, csh_last_error()); }

@@ -23,7 +23,7 @@ int png_compress(const CByteArray *inputs, size_t count, const CCSParameters *p,
 int png_convert(const CByteArray *inputs, size_t count, const CCSParameters *p, int device, CByteArray *outputs, CCSResult *results, bool lossless_webp);   // PNG -> JPEG / lossless WebP
 int rerun_to_size(const CByteArray *inputs, size_t count, const CCSParameters *p, size_t max_output_size, bool return_smallest, int device, CByteArray *outputs, CCSResult *results, bool webp);
 int webp_inputs(const CByteArray *inputs, size_t count, const CCSParameters *p, uint32_t target, int device, CByteArray *outputs, CCSResult *results);
-int gif_compress(const CByteArray *inputs, size_t count, const CCSParameters *p, int device, CByteArray *outputs, CCSResult *results);   // GIF -> GIF, the files CSH_GIF=device sends here
+int gif_compress(const CByteArray *inputs, size_t count, const CCSParameters *p, int device, CByteArray *outputs, CCSResult *results, bool lossy);   // GIF -> GIF, the files CSH_GIF=device / lossy sends here
 
 uint64_t webp_declared_pixels(const uint8_t *d, size_t n);   // capi.cpp, with cs_batch_extent
 // the alpha planes (grey pictures in device memory) of the lossy files outs[whose[j]]: the VP8L coder over them, each attached as an ALPH chunk (vp8l_encode.cpp).

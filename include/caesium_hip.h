@@ -294,11 +294,16 @@ int csh_batch_create_from_pixels_rgb(const struct csp_pixels_s *sources, size_t 
  * GIF INPUTS (libcaesium: gifski, a lossy re-quantiser).  Built here: a pixel-exact optimiser -- every canvas the output renders equals the canvas the input
  * renders; frame 0 is the whole canvas, every later frame the bounding box of what changed, unchanged pixels are written as the frame's transparent index, the LZW
  * streams are coded afresh (DESIGN.md 8.3 states the rule byte for byte).  Colour tables, delays, the loop extension and the screen descriptor are the input's;
- * comment and other application extensions are kept under keep_metadata only; gif_quality is read and ignored.  A file that does not get smaller, a file with a
+ * comment and other application extensions are kept under keep_metadata only; gif_quality is read and ignored (but see CSH_GIF=lossy below).  A file that does not get smaller, a file with a
  * plain-text extension and a file whose frames would need a colour their own table lacks come back as they are.
  * cs_batch_compress and cs_batch_compress_to_size route GIF files here when CSH_GIF=device is in the environment, read on EVERY call: unset, empty or "pass" = the
- * file is passed through as before; any other value fails every GIF of the call with CS_ERR_UNSUPPORTED and a message that names the variable.  A resize or a
- * conversion from or to GIF stays refused.  CSH_GIF_CHUNK (1024..1048576, default 16384): the pixels of an output frame one wave codes from an empty table.
+ * file is passed through as before; any other value but "lossy" fails every GIF of the call with CS_ERR_UNSUPPORTED and a message that names the variable.  A resize
+ * or a conversion from or to GIF stays refused.  CSH_GIF_CHUNK (1024..1048576, default 16384): the pixels of an output frame one wave codes from an empty table.
+ * CSH_GIF=lossy: the same route with a bounded-error LZW coder.  D = 100 - gif_quality (the quality clamped to 1..100); the coder may show, in place of a pixel's
+ * colour, another colour of the frame's table whose squared RGB distance from it is at most D * D, when that lets the current LZW match go on.  Rectangles,
+ * disposals, which pixels are transparent, tables and heads are the exact route's: every rendered pixel keeps its alpha and, where opaque, stays within D of the
+ * input's, on every frame, without drift.  gif_quality 100 (--lossless) gives the "device" file byte for byte.  The to-size call runs the route once, at the quality
+ * given, and applies the target rule.
  */
 typedef struct csg_batch csg_batch;
 enum { CSG_NKERNELS = 8 };
@@ -311,10 +316,13 @@ typedef struct {
                                         index its output code size cannot code */
     uint32_t n_not_smaller;          /* files passed through because the coded file is not smaller */
     uint32_t chunk_pixels;           /* CSH_GIF_CHUNK as this batch read it */
+    uint32_t lossy_distance;         /* D = 100 - gif_quality of a batch made by csg_batch_create_lossy; 0 for one made by csg_batch_create */
 } csg_timing;
 const char *csg_kernel_name(int slot);
 /* inputs are borrowed until csg_batch_destroy */
 int csg_batch_create(const CByteArray *inputs, size_t count, const CCSParameters *p, int device, csg_batch **out);
+/* the same batch with the bounded-error coder at p->gif_quality (CSH_GIF=lossy); csg_batch_create reads no quality */
+int csg_batch_create_lossy(const CByteArray *inputs, size_t count, const CCSParameters *p, int device, csg_batch **out);
 int csg_batch_run(csg_batch *b, csg_timing *t);
 int csg_batch_fetch(csg_batch *b, CByteArray *outputs, CCSResult *results);
 void csg_batch_destroy(csg_batch *b);
@@ -324,6 +332,10 @@ void csg_batch_destroy(csg_batch *b);
 int csg_batch_frames(csg_batch *b, size_t file, uint32_t *nframes, uint32_t *canvas_w, uint32_t *canvas_h);
 int csg_batch_read_indices(csg_batch *b, size_t file, uint32_t frame, uint8_t *dst);
 int csg_batch_read_canvas(csg_batch *b, size_t file, uint32_t frame, uint8_t *dst_rgba);
+/* after csg_batch_run: the candidate rows of the colour table frame `frame` uses, as the lossy coder reads them.  cand[b * 64 + l], l < count[b]: index b itself
+   (l = 0), then the canonical indices of the table whose colour is within D of b's, by (distance squared, index), 63 at most; bytes behind count[b] are 0.
+   A batch without a distance (D = 0) has no rows: every count is 1 */
+int csg_batch_read_near(csg_batch *b, size_t file, uint32_t frame, uint8_t *cand, uint8_t *count);
 
 #ifdef __cplusplus
 }
