@@ -27,6 +27,12 @@ struct Item {
 };
 
 // phase 0: entropy decode (k_decode*.hip)
+// grouped speculation (k_decode_par.hip k_dec_spec_group): the workgroup's lanes, and the group length by the batch's size in sub-sequences (a 1080p
+// file of the bench has 5012).  DESIGN 4.2 has the sweeps: 8 wins from 256 files up (by 0.9 ms per step at 2048), 4 at 128 files -- the CLI's device batch --,
+// 2 at 16 and 32; nothing smaller was measured, and such a batch keeps one lane per sub-sequence
+constexpr uint32_t kDecSpecLanes = 256;
+static inline uint32_t dec_group_for(uint32_t total_sub) { return total_sub >= (1u << 20) ? 8u : total_sub >= (1u << 19) ? 4u : total_sub >= (1u << 16) ? 2u : 1u; }
+
 struct DecodePlan {
     PinnedBytes bits_pool;
     std::vector<DecScan> dscans;
@@ -43,6 +49,14 @@ struct DecodePlan {
     std::vector<RefineUnit> refine_units;
     uint32_t refine_hist = 0, refine_pos = 0, refine_max_blocks = 0;   // AC refinement chains (k_decode_refine.hip): history masks, block positions, largest chain
     uint32_t total_sub = 0, max_sub = 0, max_par_blocks = 0, dc_total = 0;
+    // sub-sequences a lane of the speculation pass carries its state through (PlanSwitches::dec_group, or the planner's choice by total_sub).  1: k_dec_dense<0>,
+    // k_dec_dense<1>, list rounds; 2, 4, 8: k_dec_spec_group of spec_lanes lanes, k_dec_seed, the seam round, list rounds
+    uint32_t group = 1, spec_lanes = 256;
+    bool clear_front = false;                               // PlanSwitches::dec_clear_front: a memset in front of the phase clears the tiles, no decoding pass does (measurements)
+    std::vector<uint32_t> h_relax_cnt;                      // the host's copy of d_relax_cnt (the read-backs between the list rounds)
+    uint32_t last_run_seeds = 0, last_run_relaxed = 0;      // csh_timing.n_dec_seeds / n_dec_relaxed of the last run
+    DevBuf<uint32_t> d_seed_cnt;
+    DevBuf<uint64_t> d_seed_off;
 
     DevBuf<uint8_t> d_bits, d_clean;
     DevBuf<ParScan> d_pscans;
@@ -320,6 +334,9 @@ struct PlanSwitches {
     uint32_t list_run = CSH_LIST_RUN;   // CSH_LIST_RUN, clamped to 1..32: chunks per wave of k_list_stats, k_list_pack and k_list_refine (1: one wave per chunk)
     bool ac_runs_slot = false;  // CSH_AC_RUNS == "slot": k_ac_runs takes one wave per slot, as before it took one per 16 slots (k_ac_runs_words)
     bool ac_tiles = false;      // CSH_AC_TILES == "1": every component's AC levels are stored to its tiles, as before they lived in the lists
+    uint32_t dec_group = 0;     // CSH_DEC_GROUP: 1, 2, 4 or 8 (DecodePlan::group); 0 for anything else: the planner chooses by the batch's size
+    bool dec_clear_front = false;   // CSH_DEC_CLEAR == "front": the tiles and the EOBRUN array are cleared by memsets, not behind the speculation pass's work (what the clearing costs there: DESIGN 10)
+    uint32_t dec_lanes = 0;     // CSH_DEC_LANES: 192 or 256 lanes a workgroup of k_dec_spec_group; 0 for anything else: the default
     static PlanSwitches read();
 };
 

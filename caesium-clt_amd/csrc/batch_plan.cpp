@@ -252,6 +252,9 @@ PlanSwitches PlanSwitches::read() {
     s.fused_420 = !getenv("CSH_NO_FUSED_420");
     if (const char *lr = getenv("CSH_LIST_RUN")) { if (*lr) s.list_run = uint32_t(std::min(32, std::max(1, atoi(lr)))); }
     s.ac_runs_slot = is("CSH_AC_RUNS", "slot");
+    for (uint32_t g : {1u, 2u, 4u, 8u}) if (is("CSH_DEC_GROUP", std::to_string(g).c_str())) s.dec_group = g;
+    s.dec_clear_front = is("CSH_DEC_CLEAR", "front");
+    s.dec_lanes = is("CSH_DEC_LANES", "192") ? 192u : is("CSH_DEC_LANES", "256") ? 256u : 0u;
     return s;
 }
 
@@ -1231,6 +1234,10 @@ int BatchPlanner::upload(Laps &laps) {
         b->pix.d_rweights.upload(b->pix.rweights, st) || b->pix.d_rgb.alloc(b->pix.rgb_bytes + 64) || b->pix.d_rtmp.alloc((resize_is_fused(b->pix.max_row_in) ? 0 : b->pix.tmp_floats) + 16) || b->dec.d_need_seq_init.upload(b->dec.need_seq_init, st))
         return CS_ERR_NO_DEVICE;
     size_t nchunks = b->dec.bits_pool.size() / 64 + 1, nst = size_t(b->dec.total_sub) + b->dec.pscans.size() + 1;
+    b->dec.group = sw.dec_group ? sw.dec_group : dec_group_for(b->dec.total_sub);
+    b->dec.spec_lanes = sw.dec_lanes ? sw.dec_lanes : kDecSpecLanes;
+    b->dec.clear_front = sw.dec_clear_front;
+    if (b->dec.d_seed_cnt.alloc(b->dec.pscans.size() + 1) || b->dec.d_seed_off.alloc(b->dec.pscans.size() + 2)) return CS_ERR_NO_DEVICE;
     if (b->dec.d_clean.alloc(b->dec.bits_pool.size() + 64) || b->dec.d_unstuff_cnt.alloc(nchunks + 1) || b->dec.d_unstuff_off.alloc(nchunks + 2) ||
         b->dec.d_pstate.alloc(nst) || b->dec.d_relax_list[0].alloc(nst) || b->dec.d_relax_list[1].alloc(nst) || b->dec.d_relax_cnt.alloc(512) || b->dec.d_scan_pending.alloc(b->dec.pscans.size() + 1) || b->dec.d_cut_block.alloc(b->dec.pscans.size() + 1) || b->dec.d_claim.alloc(size_t(b->dec.total_sub) + 1) || b->dec.d_hyp.alloc((size_t(b->dec.total_sub) + 1) * 10) ||
         b->dec.d_nblk.alloc(size_t(b->dec.total_sub) + 1) || b->dec.d_blk_off.alloc(size_t(b->dec.total_sub) + 2) || b->dec.d_need_seq.alloc(b->nimg + 1) ||

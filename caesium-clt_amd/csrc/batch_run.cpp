@@ -83,7 +83,7 @@ struct Run {
         if (b->enc.d_raw.n != raw_chunks * 16) {
             if (b->enc.d_raw.alloc(raw_chunks * 16) || b->enc.d_chunk_ff.alloc(raw_chunks + 1) || b->out.d_out.alloc(b->out.out_cap + 64))
                 return -1;
-            const uint64_t longest = std::max({uint64_t(size_t(b->enc.nslots)), uint64_t(b->enc.swork.size()), uint64_t(b->dec.dc_total), uint64_t(b->dec.total_sub), uint64_t(b->dec.bits_pool.size() / 64), uint64_t(nimg)});
+            const uint64_t longest = std::max({uint64_t(size_t(b->enc.nslots)), uint64_t(b->enc.swork.size()), uint64_t(b->dec.dc_total), uint64_t(b->dec.total_sub), uint64_t(b->dec.pscans.size()), uint64_t(b->dec.bits_pool.size() / 64), uint64_t(nimg)});
             size_t tmp = exclusive_scan_tmp_bytes(longest + 1);   // the longest input any exclusive scan of a run gets
             if (b->enc.d_scan_tmp.alloc(tmp)) return -1;
         }
@@ -108,7 +108,7 @@ struct Run {
     // ---- phase 0: entropy decode (tiles must start at zero: the decoder only writes non-zero coefficients).  Where the speculation pass runs, its workgroups
     // clear the tiles on the side (k_dec_dense<0>); a memset in front of the phase otherwise (only progressive / irregular scans listed)
     int decode() {
-        const bool zero_in_spec = !b->dec.pscans.empty() && b->dec.max_sub != 0;
+        const bool spec = !b->dec.pscans.empty() && b->dec.max_sub != 0, zero_in_spec = spec && !b->dec.clear_front;
         if (!zero_in_spec) CSH_CHECK(hipMemsetAsync(b->d_coef.p, 0, size_t(b->ntiles_in) * CSH_TILE_I16 * sizeof(int16_t), st));
         if (b->out.d_status.zero(st) || b->out.d_overflow.zero(st)) return -1;
         CSH_CHECK(hipMemcpyAsync(b->dec.d_need_seq.p, b->dec.d_need_seq_init.p, size_t(nimg) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
@@ -130,40 +130,69 @@ struct Run {
             CSH_CHECK(hipMemsetAsync(b->dec.d_cut_block.p, 0xFF, b->dec.d_cut_block.n * sizeof(uint32_t), st));
             const uint64_t zero_all = uint64_t(b->ntiles_in) * CSH_TILE_I16 * sizeof(int16_t), zero_half = (zero_all / 2) & ~uint64_t(15);
             const uint64_t eob_all = (uint64_t(b->enc.d_eobrun.n) * sizeof(uint16_t)) & ~uint64_t(15), eob_half = (eob_all / 2) & ~uint64_t(15);   // (the last < 16 bytes: a memset below)
-            if (zero_in_spec) { da.zero_ptr = reinterpret_cast<uint8_t *>(b->d_coef.p); da.zero_bytes = zero_half; da.zero2_ptr = reinterpret_cast<uint8_t *>(b->enc.d_eobrun.p); da.zero2_bytes = eob_half; }
-            launch_dec_dense(st, 0, nps, b->dec.max_sub, da);
-            da.zero_bytes = 0; da.zero2_bytes = 0;
-            MARK(KS_DEC_SPEC);
-            if (nps) CSH_CHECK(hipMemsetAsync(b->dec.d_relax_cnt.p, 0, b->dec.d_relax_cnt.n * sizeof(uint32_t), st));
-            if (nps && b->dec.d_claim.zero(st)) return -1;
-            if (zero_in_spec) {   // (the other halves: k_dec_dense<1>)
-                da.zero_ptr = reinterpret_cast<uint8_t *>(b->d_coef.p) + zero_half; da.zero_bytes = zero_all - zero_half;
-                da.zero2_ptr = reinterpret_cast<uint8_t *>(b->enc.d_eobrun.p) + eob_half; da.zero2_bytes = eob_all - eob_half;
-                if (uint64_t(b->enc.d_eobrun.n) * sizeof(uint16_t) > eob_all) CSH_CHECK(hipMemsetAsync(reinterpret_cast<uint8_t *>(b->enc.d_eobrun.p) + eob_all, 0, uint64_t(b->enc.d_eobrun.n) * sizeof(uint16_t) - eob_all, st));
-                eobrun_cleared = b->enc.d_eobrun.n != 0;
+            da.live_cnt = b->dec.d_relax_cnt.p + b->dec.d_relax_cnt.n - 1; da.seed_cnt = b->dec.d_seed_cnt.p;   // (the last count: no round's)
+            const uint32_t G = spec ? b->dec.group : 1u;   // (nothing to speculate on: every launch below does nothing)
+            const int seam = G > 1 ? 1 : 0;                        // the seam round takes list 0 / count 0: list round R then reads list (R + seam) & 1 and count R + seam
+            const uint64_t eob_tail = uint64_t(b->enc.d_eobrun.n) * sizeof(uint16_t) - eob_all;
+            if (G > 1) {
+                // a lane carries its state through G sub-sequences; only the first of every group is then known to start from a guess.  Both arrays are cleared behind this pass
+                if (zero_in_spec) {
+                    da.zero_ptr = reinterpret_cast<uint8_t *>(b->d_coef.p); da.zero_bytes = zero_all; da.zero2_ptr = reinterpret_cast<uint8_t *>(b->enc.d_eobrun.p); da.zero2_bytes = eob_all;
+                    if (eob_tail) CSH_CHECK(hipMemsetAsync(reinterpret_cast<uint8_t *>(b->enc.d_eobrun.p) + eob_all, 0, eob_tail, st));
+                    eobrun_cleared = b->enc.d_eobrun.n != 0;
+                }
+                launch_dec_spec_group(st, nps, b->dec.max_sub, G, b->dec.spec_lanes, da);
+                da.zero_bytes = 0; da.zero2_bytes = 0;
+                MARK(KS_DEC_SPEC);
+                CSH_CHECK(hipMemsetAsync(b->dec.d_relax_cnt.p, 0, b->dec.d_relax_cnt.n * sizeof(uint32_t), st));
+                if (b->dec.d_claim.zero(st)) return -1;
+                // the seams in scan order, evaluated by a list round of their own: it lists what they change and does not walk
+                launch_exclusive_scan(st, b->dec.d_seed_cnt.p, b->dec.d_seed_off.p, uint64_t(nps), b->enc.d_scan_tmp.p, b->enc.d_scan_tmp.n);
+                launch_dec_seed(st, b->dec.d_seed_off.p, nps, b->dec.max_sub, G, b->dec.d_relax_list[0].p, b->dec.d_relax_cnt.p);
+                launch_dec_relax_list(st, b->dec.d_clean.p, b->dec.d_pscans.p, b->dec.total_sub, da.huffs, da.compact, b->dec.d_pstate.p, b->dec.d_nblk.p, b->dec.d_relax_list[0].p,
+                                      b->dec.d_relax_cnt.p, b->dec.d_relax_list[1].p, b->dec.d_relax_cnt.p + 1, b->dec.d_pstate.n, b->dec.d_claim.p, 0x80000000u, false);
+                MARK(KS_DEC_RELAX0);
+            } else {
+                if (zero_in_spec) { da.zero_ptr = reinterpret_cast<uint8_t *>(b->d_coef.p); da.zero_bytes = zero_half; da.zero2_ptr = reinterpret_cast<uint8_t *>(b->enc.d_eobrun.p); da.zero2_bytes = eob_half; }
+                launch_dec_dense(st, 0, nps, b->dec.max_sub, da);
+                da.zero_bytes = 0; da.zero2_bytes = 0;
+                MARK(KS_DEC_SPEC);
+                if (nps) CSH_CHECK(hipMemsetAsync(b->dec.d_relax_cnt.p, 0, b->dec.d_relax_cnt.n * sizeof(uint32_t), st));
+                if (nps && b->dec.d_claim.zero(st)) return -1;
+                if (zero_in_spec) {   // (the other halves: k_dec_dense<1>)
+                    da.zero_ptr = reinterpret_cast<uint8_t *>(b->d_coef.p) + zero_half; da.zero_bytes = zero_all - zero_half;
+                    da.zero2_ptr = reinterpret_cast<uint8_t *>(b->enc.d_eobrun.p) + eob_half; da.zero2_bytes = eob_all - eob_half;
+                    if (eob_tail) CSH_CHECK(hipMemsetAsync(reinterpret_cast<uint8_t *>(b->enc.d_eobrun.p) + eob_all, 0, eob_tail, st));
+                    eobrun_cleared = b->enc.d_eobrun.n != 0;
+                }
+                launch_dec_dense(st, 1, nps, b->dec.max_sub, da);
+                da.zero_bytes = 0; da.zero2_bytes = 0;
+                MARK(KS_DEC_RELAX0);
             }
-            launch_dec_dense(st, 1, nps, b->dec.max_sub, da);
-            da.zero_bytes = 0; da.zero2_bytes = 0;
-            MARK(KS_DEC_RELAX0);
             // list rounds until the list is empty.  How many that takes depends on the data: stock tables at ordinary quality settle
             // in ~8 (the list shrinks by 60 % a round), 50 bytes per block in ~30, 85 bytes per block in more than a hundred (a
             // wrong state then survives most of the cuts it crosses) -- so the host looks at the list length after 12 rounds and
-            // then after every 8 (a 4-byte read-back; an empty round is a ~6 us launch), up to kMaxRounds.  What is still listed
+            // then after every 8 (a read-back of the counts; an empty round is a ~6 us launch), up to kMaxRounds.  What is still listed
             // after that goes through the label chain below or to the sequential kernel.
-            const int kMaxRounds = int(b->dec.d_relax_cnt.n) - 2;
+            const int kMaxRounds = int(b->dec.d_relax_cnt.n) - 2 - seam;   // (the last count is DenseArgs::live_cnt)
+            std::vector<uint32_t> &cnt = b->dec.h_relax_cnt;
+            cnt.assign(b->dec.d_relax_cnt.n, 0u);
             int R = 0;
             for (int group = 12; nps && R < kMaxRounds; group = 8) {
                 for (int g = 0; g < group && R < kMaxRounds; g++, R++)
-                    launch_dec_relax_list(st, b->dec.d_clean.p, b->dec.d_pscans.p, b->dec.total_sub, da.huffs, da.compact, b->dec.d_pstate.p, b->dec.d_nblk.p, b->dec.d_relax_list[R & 1].p,
-                                          b->dec.d_relax_cnt.p + R, b->dec.d_relax_list[(R & 1) ^ 1].p, b->dec.d_relax_cnt.p + R + 1, b->dec.d_pstate.n, b->dec.d_claim.p, uint32_t(R + 1));
-                uint32_t left = 0;
-                CSH_CHECK(hipMemcpyAsync(&left, b->dec.d_relax_cnt.p + R, sizeof left, hipMemcpyDeviceToHost, st));
+                    launch_dec_relax_list(st, b->dec.d_clean.p, b->dec.d_pscans.p, b->dec.total_sub, da.huffs, da.compact, b->dec.d_pstate.p, b->dec.d_nblk.p, b->dec.d_relax_list[(R + seam) & 1].p,
+                                          b->dec.d_relax_cnt.p + R + seam, b->dec.d_relax_list[((R + seam) & 1) ^ 1].p, b->dec.d_relax_cnt.p + R + seam + 1, b->dec.d_pstate.n, b->dec.d_claim.p, uint32_t(R + 1));
+                // (the whole array, 2 KB: the counts in front of the last one are csh_timing's n_dec_seeds and n_dec_relaxed)
+                CSH_CHECK(hipMemcpyAsync(cnt.data(), b->dec.d_relax_cnt.p, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
                 CSH_CHECK(hipStreamSynchronize(st));
-                if (!left) break;
+                if (!cnt[size_t(R + seam)]) break;
             }
+            b->dec.last_run_seeds = cnt[0];
+            b->dec.last_run_relaxed = cnt.back();   // (G = 1: what the dense relaxation pass evaluated)
+            for (int r = 0; r < R + seam; r++) b->dec.last_run_relaxed += cnt[size_t(r)];
             if (nps) {   // scans that are still listed: settle their block-in-MCU labels exactly (k_dec_chain), or hand the image to k_decode_seq
                 if (b->dec.d_scan_pending.zero(st)) return -1;
-                launch_dec_mark_pending(st, b->dec.d_pscans.p, b->dec.total_sub, b->dec.d_relax_list[R & 1].p, b->dec.d_relax_cnt.p + R, b->dec.d_scan_pending.p);
+                launch_dec_mark_pending(st, b->dec.d_pscans.p, b->dec.total_sub, b->dec.d_relax_list[(R + seam) & 1].p, b->dec.d_relax_cnt.p + R + seam, b->dec.d_scan_pending.p);
                 da.hyp = b->dec.d_hyp.p; da.scan_pending = b->dec.d_scan_pending.p;
                 launch_dec_dense(st, 3, nps, b->dec.max_sub, da);
                 launch_dec_chain(st, b->dec.d_pscans.p, nps, b->dec.d_pstate.p, b->dec.d_nblk.p, b->dec.d_hyp.p, b->dec.d_scan_pending.p, b->dec.d_need_seq.p);
@@ -456,6 +485,7 @@ struct Run {
 int run_once(csh_batch *b, csh_timing *t, bool requant_only) {
     Run r(b, t);
     b->enc.last_run_list_runs = 0;
+    b->dec.last_run_seeds = 0; b->dec.last_run_relaxed = 0;   // (a run that does not decode reports none)
     b->enc.last_run_fused = 0; b->enc.last_run_refine = 0; b->enc.last_run_ref_packed = 0; b->enc.last_run_ac_lists = 0;
     if (r.pools() || r.marks.start()) return -1;
     // a re-run at another quality (size targeting): from the retained DCT -- unless the batch derings: the overshoot mozjpeg's deringing allows

@@ -10,6 +10,8 @@
 //            fixed point is the true state chain); the lane also counts the blocks n[t] it completes.
 //            Bit position and zig-zag index re-synchronise within a few symbols; the block-in-MCU index m
 //            only re-synchronises at luma/chroma table changes, so a 1080p scan needs ~8 shrinking rounds.
+//            Grouped (k_dec_spec_group, a batch of some size): a lane of pass A carries its state through G consecutive sub-sequences,
+//            s[t+1] = F_t(s[t]) then holds as recorded for all but the first of every group, and pass B starts from a list of those.
 //   scan    block ordinal of every cut = exclusive scan of n[t]
 //   pass W  (write): decode from the true state, store AC coefficients into the k-major tiles and DC
 //            DIFFERENCES in scan order; an exclusive scan + scatter turns them into DC values.
@@ -372,8 +374,11 @@ __device__ __forceinline__ static uint32_t decode_span(const R &rd, uint32_t w0,
     while (pos < stop_bit) step();
     // the lane in which the data ran out finishes that MCU (if the frame needs it) past its own cut: nobody else will, the
     // next lanes are beyond the data.  (A separate loop: this condition inside the hot loop doubled the kernel's time.)
+    // (at_end: data that ends exactly on this lane's cut leaves it AT the last real bit when its last symbol ends there too -- inside an MCU it is still the one to finish
+    // it: no lane follows.  Where one follows, it starts at the last real bit, is not `dead`, and finishes the MCU itself)
+    const bool at_end = stop_bit >= cx.real_bits;
     if (WRITE && !dead)
-        while (pos > cx.real_bits && (k != k_first || m != 0) && __umul24(mcu, uint32_t(cx.nb_mcu)) < cx.total_blocks) step();
+        while ((pos > cx.real_bits || (at_end && pos == cx.real_bits)) && (k != k_first || m != 0) && __umul24(mcu, uint32_t(cx.nb_mcu)) < cx.total_blocks) step();
     if (WRITE && KIND == CSH_PS_SEQ && cur_oct >= 0) flush(true);   // unfinished block: the next lane may add to this octet
     st.pos = pos; st.k = k; st.m = m;
     // WRITE: first block ordinal (relative to the segment) that stays zero because the data ran out, or 0xFFFFFFFF
@@ -543,6 +548,8 @@ __global__ void __launch_bounds__(256) k_dec_dense(DenseArgs a) {
     CSH_PHASE_LOOP(2) {
         if (phase == 0) {
             if (MODE == 1 && t < nsub && t * CSH_SUBSEQ_BYTES >= ps.clean_len) a.nblk[ps.sub_base + t] = 0;
+            // (csh_timing.n_dec_relaxed: the live sub-sequences of the scan are what this pass evaluates)
+            if (MODE == 1 && t == 0) atomicAdd(a.live_cnt, min(nsub, (ps.clean_len + CSH_SUBSEQ_BYTES - 1) / CSH_SUBSEQ_BYTES));
             if (!wg_live) continue;
             const uint32_t *src = reinterpret_cast<const uint32_t *>(&static_cast<const SET *>(a.huffs)[ps.huff_set]);
             uint32_t *dst = reinterpret_cast<uint32_t *>(&lhs);
@@ -604,6 +611,106 @@ __global__ void __launch_bounds__(256) k_dec_dense(DenseArgs a) {
         }
     }
     clear_share();
+}
+
+// ---- grouped speculation (DecodePlan::group = G > 1): a lane does not decode ONE sub-sequence from a guess, it carries its state
+// through G consecutive ones -- lane i of a workgroup owns sub-sequences G (g0 + i) .. G (g0 + i) + G - 1 of the scan (the last group
+// of a scan is shorter).  Only the group's first sub-sequence then starts from a guess; the others start from states that have run
+// 128, 256, .. bytes, and s[t+1] = F_t(s[t]) holds for them as recorded, so the lane stores n[t] with s[t+1].  What is left for the
+// relaxation are the SEAMS, the first sub-sequence of every group (k_dec_seed lists them): this pass and the seam round stand in for
+// k_dec_dense<0> + k_dec_dense<1>, which decode every sub-sequence twice to get states that have run 256 bytes.
+// A lane's look-ahead is not its neighbour's row here (that is G sub-sequences away), so every row carries its own three look-ahead
+// words: RowReader rows.  A wave stages the rows of its own 64 lanes, nine 16-byte loads a row, and nobody else reads them: between
+// the steps a wave only waits for itself.  LANES: 256 (three workgroups per CU with the compact table set) or 192 (four).
+// The workgroups also clear the tiles and the EOBRUN array behind their work, all of both: there is no second store-less pass.
+template <class SET, int LANES>
+__global__ void __launch_bounds__(LANES) k_dec_spec_group(DenseArgs a, uint32_t G) {
+    CSH_SHARED uint32_t lrows[LANES * CSH_LROW_STRIDE];
+    CSH_SHARED SET lhs;
+    CSH_PERSIST(uint64_t, carry, 1);
+    auto clear_region = [&](uint8_t *ptr, uint64_t bytes) __attribute__((always_inline)) {
+        if (!bytes) return;
+        const uint64_t nwg = uint64_t(gridDim.x) * gridDim.y, wg = uint64_t(blockIdx.y) * gridDim.x + blockIdx.x;
+        const uint64_t share = ((bytes / 16 + nwg - 1) / nwg) * 16, z0 = wg * share, z1 = z0 + share < bytes ? z0 + share : bytes;
+        for (uint64_t off = z0 + uint64_t(threadIdx.x) * 16; off < z1; off += LANES * 16) {
+#ifdef CSH_EMUL
+            memset(ptr + off, 0, 16);
+#else
+            __builtin_nontemporal_store(0ull, reinterpret_cast<unsigned long long *>(ptr + off));
+            __builtin_nontemporal_store(0ull, reinterpret_cast<unsigned long long *>(ptr + off + 8));
+#endif
+        }
+    };
+    const ParScan &ps = a.pss[blockIdx.y];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t nsub = (ps.bits_len + CSH_SUBSEQ_BYTES - 1) / CSH_SUBSEQ_BYTES;
+    const uint32_t live_sub = par_decoded(ps.kind) ? min(nsub, (ps.clean_len + CSH_SUBSEQ_BYTES - 1) / CSH_SUBSEQ_BYTES) : 0u;
+    if (blockIdx.x == 0 && tid == 0) a.seed_cnt[blockIdx.y] = (live_sub + G - 1) / G;   // the seams k_dec_seed lists for this scan
+    if (!par_decoded(ps.kind)) { clear_region(a.zero_ptr, a.zero_bytes); clear_region(a.zero2_ptr, a.zero2_bytes); return; }
+    const uint32_t g0 = blockIdx.x * LANES, wave0 = tid & ~63u, lane = tid & 63u;
+    const bool wg_live = g0 * G < live_sub;
+    PReader g; g.base = a.clean + ps.bits_off; g.len = ps.clean_len;
+    const size_t base = ps.sub_base + ps.par_index;
+    CSH_PHASE_LOOP_MIXED(2 * int(G), 0xFFFFFFFEu) {   // phase 2j: stage the lanes' j-th rows (and, j = 0, the tables: a barrier), 2j + 1: decode them
+        const uint32_t j = uint32_t(phase) >> 1;
+        if (!(phase & 1)) {
+            if (phase == 0) {
+                for (uint32_t jj = 0; jj < G; jj++) {   // past the data: no blocks (the write pass's ordinals are sums over every sub-sequence)
+                    const uint32_t t = (g0 + tid) * G + jj;
+                    if (t < nsub && t >= live_sub) a.nblk[ps.sub_base + t] = 0;
+                }
+                if (wg_live) {
+                    const uint32_t *src = reinterpret_cast<const uint32_t *>(&static_cast<const SET *>(a.huffs)[ps.huff_set]);
+                    uint32_t *dst = reinterpret_cast<uint32_t *>(&lhs);
+                    for (uint32_t i = tid; i < sizeof(SET) / 4; i += LANES) dst[i] = src[i];
+                }
+            }
+            if (!wg_live) continue;
+            for (uint32_t idx = lane; idx < 64 * 9; idx += 64) {   // 144 contiguous bytes a row: eight lanes its 128, a ninth the look-ahead
+                const uint32_t row = wave0 + idx / 9, q = idx % 9, t = (g0 + row) * G + j;
+                if (t >= live_sub) continue;
+                uint32_t *dst = lrows + row * CSH_LROW_STRIDE + q * 4;
+                const uint32_t b = t * CSH_SUBSEQ_BYTES + q * 16, nw = q == 8 ? CSH_LROW_WORDS - 32 : 4;
+                if (b + 16 <= g.len) {
+                    uint32_t w[4];
+#ifdef CSH_EMUL
+                    memcpy(w, g.base + b, 16);
+#else
+                    const uint4 v = *reinterpret_cast<const uint4 *>(g.base + b);   // (segments start on 64-byte boundaries of the pool)
+                    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+#endif
+                    for (uint32_t i = 0; i < nw; i++) dst[i] = (w[i] >> 24) | ((w[i] >> 8) & 0xFF00u) | ((w[i] << 8) & 0xFF0000u) | (w[i] << 24);
+                } else
+                    for (uint32_t i = 0; i < nw; i++) dst[i] = g.word(b / 4 + i);
+            }
+            continue;
+        }
+        if (!wg_live) continue;
+        const uint32_t t = (g0 + tid) * G + j;
+        if (t >= nsub) continue;
+        PState st;
+        if (j == 0) {
+            st.pos = t * CSH_SUBSEQ_BYTES * 8; st.m = 0; st.k = ps.kind == CSH_PS_AC_FIRST ? ps.Ss : 0;
+            if (t == 0) a.state[base] = pack_state(st);
+        } else st = unpack_state(carry[0]);
+        if (t >= live_sub) { a.state[base + t + 1] = 0; continue; }
+        RowReader rd; rd.row = lrows + tid * CSH_LROW_STRIDE;
+        const ParCtx cx = make_ctx(ps, nullptr);
+        const uint32_t n = CSH_SPAN(false, ps.kind, rd, t * (CSH_SUBSEQ_BYTES / 4), reinterpret_cast<const uint8_t *>(&lhs), uint32_t(sizeof(SET::root)), cx, st,
+                                    (t + 1) * CSH_SUBSEQ_BYTES * 8, 0, nullptr, nullptr, nullptr);
+        carry[0] = pack_state(st);
+        a.state[base + t + 1] = carry[0];
+        if (j) a.nblk[ps.sub_base + t] = n;   // (from the recorded s[t]; a seam's count comes from the seam round)
+    }
+    clear_region(a.zero_ptr, a.zero_bytes);
+    clear_region(a.zero2_ptr, a.zero2_bytes);
+}
+// the seams of every scan, in scan order, as the work list of the first list round: seed_off = exclusive scan of k_dec_spec_group's seed_cnt
+__global__ void __launch_bounds__(256) k_dec_seed(const uint64_t *seed_off, int nps, uint32_t G, uint64_t *list, uint32_t *cnt) {
+    const uint32_t si = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t o = seed_off[si];
+    if (i < uint32_t(seed_off[si + 1] - o)) list[o + i] = (uint64_t(si) << 32) | (i * G);
+    if (blockIdx.x == 0 && si == 0 && threadIdx.x == 0) *cnt = uint32_t(seed_off[nps]);
 }
 
 // DC: prefix sums of the differences (scan order) -> absolute DC at zig-zag row 0 of the tiles
@@ -668,15 +775,30 @@ void launch_dec_dense(hipStream_t st, int mode, int nps, uint32_t max_sub, const
     else CSH_DENSE(3);
 #undef CSH_DENSE
 }
+void launch_dec_spec_group(hipStream_t st, int nps, uint32_t max_sub, uint32_t group, uint32_t lanes, const DenseArgs &a) {
+    if (!nps || !max_sub) return;
+    const uint32_t ngroups = (max_sub + group - 1) / group;
+#define CSH_SPEC(L) do { const dim3 grid((ngroups + L - 1) / L, nps);                                                                        \
+                         if (a.compact) CSH_LAUNCH_PHASED((k_dec_spec_group<ParHuffSet4, L>), 2 * int(group), grid, dim3(L), st, a, group); \
+                         else CSH_LAUNCH_PHASED((k_dec_spec_group<ParHuffSet, L>), 2 * int(group), grid, dim3(L), st, a, group); } while (0)
+    if (lanes == 192) CSH_SPEC(192);
+    else CSH_SPEC(256);
+#undef CSH_SPEC
+}
+void launch_dec_seed(hipStream_t st, const uint64_t *seed_off, int nps, uint32_t max_sub, uint32_t group, uint64_t *list, uint32_t *cnt) {
+    if (!nps || !max_sub) return;
+    CSH_LAUNCH(k_dec_seed, dim3(((max_sub + group - 1) / group + 255) / 256, nps), dim3(256), st, seed_off, nps, group, list, cnt);
+}
 #ifdef CSH_EMUL
 int csh_emul_jacobi = 0;  // tests: make a list round read the states as they were BEFORE the launch (what concurrent lanes see at worst)
 #endif
 void launch_dec_relax_list(hipStream_t st, const uint8_t *clean, const ParScan *ps, uint32_t total_sub, const void *huffs, int compact, uint64_t *state, uint32_t *nblk,
-                           const uint64_t *list_in, const uint32_t *cnt_in, uint64_t *list_out, uint32_t *cnt_out, size_t nstate, uint32_t *claim, uint32_t epoch) {
+                           const uint64_t *list_in, const uint32_t *cnt_in, uint64_t *list_out, uint32_t *cnt_out, size_t nstate, uint32_t *claim, uint32_t epoch, bool walk) {
     // walking starts when the list is down to 0.1 % of the sub-sequences, or after ten launches whatever its size: files of
     // ordinary quality are through by then (their lists shrink by 60 % a launch and walking would only make their waves wait
     // for the walkers), what is left is slow-to-synchronise data that needs it
-    const uint32_t walk_below = epoch > 10 ? 0xFFFFFFFFu : total_sub / 1024 + 1;
+    // (walk false: the seam round behind a grouped speculation pass -- its list is one sub-sequence in G and none of them has been evaluated yet)
+    const uint32_t walk_below = !walk ? 0u : epoch > 10 ? 0xFFFFFFFFu : total_sub / 1024 + 1;
     if (!total_sub) return;
     const uint64_t *state_rd = state;
 #ifdef CSH_EMUL

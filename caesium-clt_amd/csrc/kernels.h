@@ -61,10 +61,16 @@ struct DenseArgs {
     uint32_t *cut_block;   // per segment: first block that stays zero because the data ran out (0xFFFFFFFF: none), write pass -> k_dc_scatter
     uint8_t *zero_ptr; uint64_t zero_bytes;   // the store-less passes (modes 0, 1): a region their workgroups clear between them -- the coefficient tiles, which the write pass needs at zero (a multiple of 16 bytes)
     uint8_t *zero2_ptr; uint64_t zero2_bytes; // a second one: the encoder's EOBRUN array (4 GB per 2048 files, cleared for every run)
+    uint32_t *live_cnt;    // mode 1 adds the sub-sequences it evaluates (csh_timing.n_dec_relaxed)
+    uint32_t *seed_cnt;    // grouped speculation: per scan, the seams the first list round starts from
 };
 void launch_dec_dense(hipStream_t st, int mode /*0 speculate, 1 relax, 2 write*/, int nps, uint32_t max_sub, const DenseArgs &a);
+// grouped speculation (DecodePlan::group > 1): a lane carries its state through `group` consecutive sub-sequences, `lanes` (256 or 192) lanes a workgroup;
+// launch_dec_seed then lists the first sub-sequence of every group (seed_off: the exclusive scan of DenseArgs::seed_cnt) for a list round that does not walk
+void launch_dec_spec_group(hipStream_t st, int nps, uint32_t max_sub, uint32_t group, uint32_t lanes, const DenseArgs &a);
+void launch_dec_seed(hipStream_t st, const uint64_t *seed_off, int nps, uint32_t max_sub, uint32_t group, uint64_t *list, uint32_t *cnt);
 void launch_dec_relax_list(hipStream_t st, const uint8_t *clean, const ParScan *ps, uint32_t total_sub, const void *huffs, int compact, uint64_t *state, uint32_t *nblk,
-                           const uint64_t *list_in, const uint32_t *cnt_in, uint64_t *list_out, uint32_t *cnt_out, size_t nstate, uint32_t *claim, uint32_t epoch);
+                           const uint64_t *list_in, const uint32_t *cnt_in, uint64_t *list_out, uint32_t *cnt_out, size_t nstate, uint32_t *claim, uint32_t epoch, bool walk = true);
 // progressive inputs: one wave per chain of scans (k_decode_prog.hip); images with need_seq == 4
 // AC refinement chains of progressive inputs (k_decode_refine.hip): history masks, the serial parse (one wave per chain), the parallel apply
 void launch_refine_chains(hipStream_t st, const uint8_t *clean, const ParScan *pss, const ParHuffSet *huffs, const DecScan *scans, const ProgChain *chains,

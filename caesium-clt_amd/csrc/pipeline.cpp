@@ -274,6 +274,7 @@ static int batch_run(csh_batch *b, csh_timing *t, bool requant_only) {
         t->n_ac_in_lists = b->enc.last_run_ac_lists;
         t->n_list_runs = b->enc.last_run_list_runs;
         t->n_ref_packed = b->enc.last_run_ref_packed;
+        t->n_dec_group = b->dec.group; t->n_dec_seeds = b->dec.last_run_seeds; t->n_dec_relaxed = b->dec.last_run_relaxed;
         for (const Item &it : b->items) if (it.image < 0) t->n_failed++;
         for (int i = 0; i < b->nimg; i++) { t->out_bytes += b->out.h_img_size[i]; t->pixels += uint64_t(b->imgs[i].width) * b->imgs[i].height; }
         t->in_bytes = b->dec.bits_pool.size();

@@ -146,6 +146,12 @@ typedef struct {
                                      quantiser's statistics scans and the scan search's candidates included).  0 for sequential output */
     uint32_t n_ref_packed;        /* of n_list_refine, the work items whose bits this run packed from the lists as well (k_list_refine_pack): no token was written for them.
                                      0 with CSH_REF_PACK=0 (tokens and k_pack, as before), with CSH_REF_LIST=0 and for sequential output */
+    uint32_t n_dec_group;         /* consecutive 128-byte sub-sequences a lane of the parallel decoder's speculation pass carried its state through: CSH_DEC_GROUP (1, 2, 4, 8), or
+                                     what the planner chose for the batch's size.  1: every sub-sequence is speculated from a guess and relaxed once by a dense pass */
+    uint32_t n_dec_seeds;         /* sub-sequences on the relaxation list in front of its first round.  n_dec_group > 1: the first sub-sequence of every group, the sum over the
+                                     parallel-decoded scans and restart segments of ceil(live sub-sequences / n_dec_group); 1: what the dense relaxation pass listed */
+    uint32_t n_dec_relaxed;       /* sub-sequence evaluations the relaxation asked for in this run: the sum of the list's length in front of every round, the seam round included
+                                     (n_dec_group = 1: plus the live sub-sequences, which the dense relaxation pass evaluated).  Sub-sequences a lane walked on into are not counted */
 } csh_timing;
 
 int csh_device_count(void);
