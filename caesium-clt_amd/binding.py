@@ -39,6 +39,11 @@ class GifTiming(C.Structure):
                 ("n_failed", C.c_uint32), ("n_passed_palette", C.c_uint32), ("n_not_smaller", C.c_uint32), ("chunk_pixels", C.c_uint32), ("lossy_distance", C.c_uint32)]
 
 
+class TiffTiming(C.Structure):
+    _fields_ = [("total_ms", C.c_float), ("kernel_ms", C.c_float * 11), ("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("n_files", C.c_uint32), ("n_pages", C.c_uint32),
+                ("n_segments", C.c_uint32), ("n_passed", C.c_uint32), ("n_failed", C.c_uint32), ("strip_bytes", C.c_uint32), ("n_pred_won", C.c_uint32), ("n_pred_lost", C.c_uint32)]
+
+
 class CaesiumError(RuntimeError):
     def __init__(self, code, message):
         super().__init__(f"[{code}] {message}")
@@ -57,6 +62,9 @@ EXPORTS = ["cs_default_parameters", "cs_compress_in_memory", "cs_compress_to_siz
            "cswd_batch_create", "cswd_batch_run", "cswd_batch_pixels", "cswd_batch_read_pixels", "cswd_batch_alpha", "cswd_batch_read_rgba", "cswd_batch_destroy", "cswd_batch_frames", "cswd_batch_read_canvas", "cswd_batch_encode_anim", "cswd_rgba_join", "cswd_rgba_destroy", "csh_batch_create_webp_from_pixels", "csh_batch_create_from_pixels_rgb", "csl_encode_pixels", "csl_attach_alpha"]
 # the GIF batch's entry points (the csg_ prefix): a list of their own, beside the one above
 GIF_EXPORTS = ["csg_kernel_name", "csg_batch_create", "csg_batch_run", "csg_batch_fetch", "csg_batch_destroy", "csg_batch_frames", "csg_batch_read_indices", "csg_batch_read_canvas", "csg_batch_create_lossy", "csg_batch_read_near"]
+# the TIFF batch's entry points (the cst_ prefix)
+TIFF_EXPORTS = ["cst_kernel_name", "cst_batch_create", "cst_batch_run", "cst_batch_fetch", "cst_batch_destroy", "cst_batch_pages", "cst_batch_page_info", "cst_batch_read_decoded"]
+TIFF_OUT = {"none": 0, "lzw": 1, "packbits": 3}   # cst_batch_create's compression (CST_OUT_*): tiff_compression's numbering
 
 
 def _declare(L):
@@ -134,6 +142,16 @@ def _declare(L):
     L.csg_batch_read_canvas.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
     L.csg_batch_create_lossy.argtypes = [P(CByteArray), C.c_size_t, P(CCSParameters), C.c_int, P(C.c_void_p)]
     L.csg_batch_read_near.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.cst_kernel_name.argtypes = [C.c_int]
+    L.cst_kernel_name.restype = C.c_char_p
+    L.cst_batch_create.argtypes = [P(CByteArray), C.c_size_t, P(CCSParameters), C.c_int, C.c_int, P(C.c_void_p)]
+    L.cst_batch_run.argtypes = [C.c_void_p, P(TiffTiming)]
+    L.cst_batch_fetch.argtypes = [C.c_void_p, P(CByteArray), P(CCSResult)]
+    L.cst_batch_destroy.argtypes = [C.c_void_p]
+    L.cst_batch_destroy.restype = None
+    L.cst_batch_pages.argtypes = [C.c_void_p, C.c_size_t, P(C.c_uint32)]
+    L.cst_batch_page_info.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, P(C.c_uint32), P(C.c_uint32), P(C.c_uint32), P(C.c_uint32), P(C.c_uint32), P(C.c_uint64)]
+    L.cst_batch_read_decoded.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
     return L
 
 
@@ -409,6 +427,81 @@ class GifBatch:
             pass
 
 
+class TiffBatch:
+    """cst_batch: a group of TIFF files, their strips and tiles decoded and coded again on the device (the route CSH_TIFF selects); compression: "none", "lzw" or
+    "packbits"."""
+
+    def __init__(self, api, blobs, params, compression="lzw", device=0):
+        self.api = api
+        L = api.L
+        self.n = len(blobs)
+        self._keep = [C.create_string_buffer(b, len(b)) for b in blobs]
+        self._in = (CByteArray * self.n)()
+        for i, buf in enumerate(self._keep):
+            self._in[i].data = C.cast(buf, C.POINTER(C.c_uint8))
+            self._in[i].length = len(blobs[i])
+        self.h = C.c_void_p()
+        rc = L.cst_batch_create(self._in, self.n, C.byref(params), TIFF_OUT[compression], device, C.byref(self.h))
+        if rc:
+            raise CaesiumError(rc, L.csh_last_error().decode())
+
+    def run(self):
+        t = TiffTiming()
+        rc = self.api.L.cst_batch_run(self.h, C.byref(t))
+        if rc:
+            raise CaesiumError(rc, self.api.L.csh_last_error().decode())
+        return t
+
+    def fetch(self):
+        L = self.api.L
+        outs = (CByteArray * self.n)()
+        res = (CCSResult * self.n)()
+        if L.cst_batch_fetch(self.h, outs, res) < 0:
+            raise CaesiumError(-1, L.csh_last_error().decode())
+        result = []
+        for i in range(self.n):
+            result.append(C.string_at(outs[i].data, outs[i].length) if res[i].success else CaesiumError(res[i].code, (res[i].error_message or b"").decode()))
+            L.cs_free_bytes(C.byref(outs[i])); L.cs_free_result(C.byref(res[i]))
+        return result
+
+    def pages(self, file):
+        """-> page count; CaesiumError for a file that failed (its code) or is passed through (-2)"""
+        n = C.c_uint32()
+        rc = self.api.L.cst_batch_pages(self.h, file, C.byref(n))
+        if rc:
+            raise CaesiumError(rc, "the file failed" if rc > 0 else self.api.L.csh_last_error().decode())
+        return n.value
+
+    def page_info(self, file, page):
+        """-> dict(width, height, rowbytes, nsegments, tiled, decoded_bytes): the input page as the walk read it"""
+        v = [C.c_uint32() for _ in range(5)]
+        nb = C.c_uint64()
+        rc = self.api.L.cst_batch_page_info(self.h, file, page, *[C.byref(x) for x in v], C.byref(nb))
+        if rc:
+            raise CaesiumError(rc, "the file failed" if rc > 0 else self.api.L.csh_last_error().decode())
+        return dict(width=v[0].value, height=v[1].value, rowbytes=v[2].value, nsegments=v[3].value, tiled=bool(v[4].value), decoded_bytes=nb.value)
+
+    def decoded(self, file, page):
+        """the page's decoded bytes, predictor undone, the input's segments back to back"""
+        import numpy as np
+        a = np.empty(self.page_info(file, page)["decoded_bytes"], dtype=np.uint8)
+        rc = self.api.L.cst_batch_read_decoded(self.h, file, page, a.ctypes.data)
+        if rc:
+            raise CaesiumError(rc, self.api.L.csh_last_error().decode())
+        return a.tobytes()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.api.L.cst_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class CaesiumHip:
     def __init__(self, path=None):
         path = path or library_path()
@@ -551,6 +644,12 @@ class CaesiumHip:
 
     def gif_kernel_names(self):
         return [self.L.csg_kernel_name(i).decode() for i in range(8)]
+
+    def tiff_batch(self, blobs, params=None, compression="lzw", device=0):
+        return TiffBatch(self, blobs, params or default_parameters(), compression, device)
+
+    def tiff_kernel_names(self):
+        return [self.L.cst_kernel_name(i).decode() for i in range(11)]
 
     def gif_canvases(self, blobs, device=0):
         """GIF files -> per file an array [frames][H][W][4] uint8: every canvas as the device walk composes it (transparent index and disposal applied, 0 where

@@ -213,8 +213,15 @@ bool parse_args(const std::vector<std::string> &args_in, Options &o, std::string
 
 // ------------------------------------------------------------------------------------------------ scan
 static std::string lower(std::string s) { for (char &c : s) c = (char)tolower((unsigned char)c); return s; }
+// TIFF files join the scan only while CSH_TIFF sends them to the library's TIFF route (set, and not "pass"): the reference's scanner knows none, and without the
+// variable this one is the reference's
+static bool tiff_route_on() {
+    const char *e = getenv("CSH_TIFF");
+    return e && *e && strcmp(e, "pass") != 0;
+}
 bool has_supported_extension(const fs::path &p) {
     std::string e = lower(p.extension().string());
+    if ((e == ".tif" || e == ".tiff") && tiff_route_on()) return true;
     return e == ".jpg" || e == ".jpeg" || e == ".png" || e == ".webp" || e == ".gif";
 }
 bool is_filetype_supported(const fs::path &p) {
@@ -228,6 +235,7 @@ bool is_filetype_supported(const fs::path &p) {
     if (!memcmp(b, "\x89PNG", 4)) return true;
     if (!memcmp(b, "RIFF", 4) && !memcmp(b + 8, "WEBP", 4)) return true;
     if (!memcmp(b, "GIF8", 4)) return true;
+    if ((!memcmp(b, "II*\0", 4) || !memcmp(b, "MM\0*", 4)) && tiff_route_on()) return true;
     return false;
 }
 // std::path::absolute (Unix): prepend the cwd to relative paths, drop `.` components and repeated separators, keep `..`

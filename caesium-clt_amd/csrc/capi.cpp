@@ -59,6 +59,8 @@ static uint64_t declared_pixels(const uint8_t *d, size_t n) {
 // A GIF file leaves this path under CSH_GIF=device (read on every call; unset, empty or "pass": here as before): route::gif_compress optimises it, pixel-exact
 // (DESIGN.md 8.3), and under CSH_GIF=lossy with the bounded-error coder at gif_quality; its resize is still answered here, and any other value of the variable
 // fails the call's GIF files with CS_ERR_UNSUPPORTED.
+// A TIFF file leaves it when CSH_TIFF is set (tiff_mode below; read on every call): route::tiff_compress decodes its strips and tiles and codes them again;
+// its resize is still answered here.
 static CCSResult passthrough(const CByteArray &in, const CCSParameters *p, CByteArray *out) {
     out->data = nullptr; out->length = 0;
     if (p->width || p->height) return make_result(CS_ERR_UNSUPPORTED, "resizing a GIF / TIFF file has no path in this build (the file itself is passed through without a size)");
@@ -67,23 +69,40 @@ static CCSResult passthrough(const CByteArray &in, const CCSParameters *p, CByte
     memcpy(out->data, in.data, in.length); out->length = in.length;
     return make_result(0, nullptr);
 }
+static const char *const BAD_CSH_GIF = "CSH_GIF names no GIF path (unset, empty or \"pass\": the file is passed through; \"device\": the pixel-exact optimiser; \"lossy\": the same with the bounded-error coder at gif_quality)";
+static const char *const BAD_CSH_TIFF = "CSH_TIFF names no TIFF path (unset, empty or \"pass\": the file is passed through; \"device\": re-coded with the compression tiff_compression names; \"lzw\", \"packbits\", \"none\": re-coded with that compression)";
+static const char *const NO_TIFF_DEFLATE = "the TIFF route's Deflate coder is not built (tiff_compression 2 under CSH_TIFF=device): LZW (1), PackBits (3) and uncompressed output are";
 // CSH_GIF: 0 pass the file through, 1 the device route, 2 the device route with the lossy coder at gif_quality, -1 a value that names none of them
 static int gif_mode() {
     const char *e = getenv("CSH_GIF");
     if (!e || !*e || !strcmp(e, "pass")) return 0;
     return !strcmp(e, "device") ? 1 : !strcmp(e, "lossy") ? 2 : -1;
 }
-// the files of a compress call by the row that takes them; a TIFF file, and a GIF file outside CSH_GIF=device, is answered on the spot, by pass(i) -- or by
-// refuse(i) under a value of CSH_GIF that means nothing
-struct Rows { std::vector<size_t> png, webp, gif, other; bool any_pass = false, gif_lossy = false; };
+// CSH_TIFF: TIFF_PASS the file is passed through; a CST_OUT_* value: the device route with that output compression ("device": what tiff_compression names -- 1 LZW,
+// 3 PackBits, 2 Deflate, which the route does not write: TIFF_NO_DEFLATE; anything else uncompressed); TIFF_JUNK: a value that names none of them
+enum { TIFF_PASS = -1, TIFF_JUNK = -2, TIFF_NO_DEFLATE = -3 };
+static int tiff_mode(const CCSParameters *p) {
+    const char *e = getenv("CSH_TIFF");
+    if (!e || !*e || !strcmp(e, "pass")) return TIFF_PASS;
+    if (!strcmp(e, "lzw")) return CST_OUT_LZW;
+    if (!strcmp(e, "packbits")) return CST_OUT_PACKBITS;
+    if (!strcmp(e, "none")) return CST_OUT_NONE;
+    if (strcmp(e, "device")) return TIFF_JUNK;
+    return p->tiff_compression == 1 ? int(CST_OUT_LZW) : p->tiff_compression == 3 ? int(CST_OUT_PACKBITS) : p->tiff_compression == 2 ? int(TIFF_NO_DEFLATE) : int(CST_OUT_NONE);
+}
+// the files of a compress call by the row that takes them; a TIFF file without CSH_TIFF, and a GIF file outside CSH_GIF=device, is answered on the spot, by pass(i) -- or by
+// refuse(i, message) under a value of CSH_GIF / CSH_TIFF that means nothing (and for a TIFF file under CSH_TIFF=device with tiff_compression 2)
+struct Rows { std::vector<size_t> png, webp, gif, tiff, other; bool any_pass = false, gif_lossy = false; int tiff_out = 0; };
 template <class Pass, class Refuse>
 static Rows sort_rows(const CByteArray *inputs, size_t count, const CCSParameters *p, Pass pass, Refuse refuse) {
     Rows r;
-    const int gif = gif_mode();
-    r.gif_lossy = gif == 2;
+    const int gif = gif_mode(), tiff = tiff_mode(p);
+    r.gif_lossy = gif == 2; r.tiff_out = tiff;
     for (size_t i = 0; i < count; i++) {
         const int t = sniff(inputs[i].data, inputs[i].length);
-        if (t == CS_TYPE_GIF && gif < 0) { refuse(i); r.any_pass = true; }
+        if (t == CS_TYPE_GIF && gif < 0) { refuse(i, BAD_CSH_GIF); r.any_pass = true; }
+        else if (t == CS_TYPE_TIFF && (tiff == TIFF_JUNK || tiff == TIFF_NO_DEFLATE) && !p->width && !p->height) { refuse(i, tiff == TIFF_JUNK ? BAD_CSH_TIFF : NO_TIFF_DEFLATE); r.any_pass = true; }
+        else if (t == CS_TYPE_TIFF && tiff >= 0 && !p->width && !p->height) r.tiff.push_back(i);
         else if (t == CS_TYPE_GIF && gif > 0 && !p->width && !p->height) r.gif.push_back(i);
         else if (t == CS_TYPE_GIF || t == CS_TYPE_TIFF) { pass(i); r.any_pass = true; }
         else (t == CS_TYPE_PNG ? r.png : t == CS_TYPE_WEBP ? r.webp : r.other).push_back(i);
@@ -92,8 +111,6 @@ static Rows sort_rows(const CByteArray *inputs, size_t count, const CCSParameter
 }
 
 // A caller may pass no results array: the routes always write one, so such a call gets an array of its own here, released when the call returns
-static const char *const BAD_CSH_GIF = "CSH_GIF names no GIF path (unset, empty or \"pass\": the file is passed through; \"device\": the pixel-exact optimiser; \"lossy\": the same with the bounded-error coder at gif_quality)";
-
 struct Results {
     std::vector<CCSResult> own;
     CCSResult *r;
@@ -159,14 +176,15 @@ int cs_batch_compress(const CByteArray *inputs, size_t count, const CCSParameter
     CCSResult *results = own.r;
     int passed_failed = 0;
     const Rows r = sort_rows(inputs, count, p, [&](size_t i) { results[i] = passthrough(inputs[i], p, &outputs[i]); if (!results[i].success) passed_failed++; },
-                             [&](size_t i) { outputs[i].data = nullptr; outputs[i].length = 0; results[i] = make_result(CS_ERR_UNSUPPORTED, BAD_CSH_GIF); passed_failed++; });
-    const std::vector<size_t> &png = r.png, &webp = r.webp, &gif = r.gif, &other = r.other;   // PNG files: lossless under png.optimize, else the lossy (quantising) form of the same pipeline
-    if (png.empty() && webp.empty() && gif.empty() && !r.any_pass) return route::jpeg_compress(inputs, count, p, device, outputs, results);
+                             [&](size_t i, const char *msg) { outputs[i].data = nullptr; outputs[i].length = 0; results[i] = make_result(CS_ERR_UNSUPPORTED, msg); passed_failed++; });
+    const std::vector<size_t> &png = r.png, &webp = r.webp, &gif = r.gif, &tiff = r.tiff, &other = r.other;   // PNG files: lossless under png.optimize, else the lossy (quantising) form of the same pipeline
+    if (png.empty() && webp.empty() && gif.empty() && tiff.empty() && !r.any_pass) return route::jpeg_compress(inputs, count, p, device, outputs, results);
     std::atomic<int> failed{0};
     auto run = [&](const std::vector<size_t> &idx, int kind) {
         failed += route::for_subset(inputs, idx, outputs, results, [&](const CByteArray *in, size_t n, CByteArray *out, CCSResult *res) {
             return kind == 1 ? route::png_compress(in, n, p, device, out, res, false) : kind == 2 ? route::webp_inputs(in, n, p, CS_TYPE_WEBP, device, out, res) :
-                   kind == 3 ? route::gif_compress(in, n, p, device, out, res, r.gif_lossy) : route::jpeg_compress(in, n, p, device, out, res);
+                   kind == 3 ? route::gif_compress(in, n, p, device, out, res, r.gif_lossy) : kind == 4 ? route::tiff_compress(in, n, p, device, out, res, r.tiff_out) :
+                   route::jpeg_compress(in, n, p, device, out, res);
         });
     };
     // the rows side by side (each batch keeps to its own stream; their outputs are disjoint): a tree of all three kinds waits for its slowest row only
@@ -174,6 +192,7 @@ int cs_batch_compress(const CByteArray *inputs, size_t count, const CCSParameter
     if (!png.empty() && (!webp.empty() || !other.empty())) rows.emplace_back(run, std::cref(png), 1); else run(png, 1);
     if (!webp.empty() && !other.empty()) rows.emplace_back(run, std::cref(webp), 2); else run(webp, 2);
     if (!gif.empty() && !other.empty()) rows.emplace_back(run, std::cref(gif), 3); else run(gif, 3);
+    if (!tiff.empty() && !other.empty()) rows.emplace_back(run, std::cref(tiff), 4); else run(tiff, 4);
     run(other, 0);
     for (std::thread &t : rows) t.join();
     return failed.load() + passed_failed;
@@ -200,12 +219,15 @@ int cs_batch_compress_to_size(const CByteArray *inputs, size_t count, CCSParamet
         results[i] = passthrough(inputs[i], p, &outputs[i]);
         if (!results[i].success) failed++;
         hold_to_target(i, "the file is passed through as it is (GIF / TIFF have no device path) and is larger than the target size");
-    }, [&](size_t i) { outputs[i].data = nullptr; outputs[i].length = 0; results[i] = make_result(CS_ERR_UNSUPPORTED, BAD_CSH_GIF); failed++; });
+    }, [&](size_t i, const char *msg) { outputs[i].data = nullptr; outputs[i].length = 0; results[i] = make_result(CS_ERR_UNSUPPORTED, msg); failed++; });
     // a GIF file under CSH_GIF=device / lossy: one run of its route (the optimiser is pixel-exact, and the lossy coder runs at the quality given: no quality is walked), then the same rule
     failed += route::for_subset(inputs, rows.gif, outputs, results, [&](const CByteArray *in, size_t n, CByteArray *out, CCSResult *res) { return route::gif_compress(in, n, p, device, out, res, rows.gif_lossy); });
     for (size_t i : rows.gif) hold_to_target(i, rows.gif_lossy ? "the GIF route runs once, at the quality given, and walks no quality: its one result is larger than the target size"
                                                                : "the GIF optimiser is pixel-exact and has no quality to walk: its one result is larger than the target size");
-    if (rows.png.empty() && rows.webp.empty() && rows.gif.empty() && !rows.any_pass) return route::jpeg_compress_to_size(inputs, count, p, max_output_size, return_smallest, device, outputs, results);
+    // a TIFF file with CSH_TIFF set: one run of its route (lossless: there is no quality to walk), then the same rule
+    failed += route::for_subset(inputs, rows.tiff, outputs, results, [&](const CByteArray *in, size_t n, CByteArray *out, CCSResult *res) { return route::tiff_compress(in, n, p, device, out, res, rows.tiff_out); });
+    for (size_t i : rows.tiff) hold_to_target(i, "the TIFF route is lossless and has no quality to walk: its one result is larger than the target size");
+    if (rows.png.empty() && rows.webp.empty() && rows.gif.empty() && rows.tiff.empty() && !rows.any_pass) return route::jpeg_compress_to_size(inputs, count, p, max_output_size, return_smallest, device, outputs, results);
     // the JPEG walk leaves its last quality in the caller's parameters, as the reference's &mut does
     failed += route::for_subset(inputs, rows.other, outputs, results, [&](const CByteArray *in, size_t n, CByteArray *out, CCSResult *res) {
         return route::jpeg_compress_to_size(in, n, p, max_output_size, return_smallest, device, out, res);

@@ -1,5 +1,5 @@
 // routes.hpp -- what capi.cpp's entry points route their files through: one function per kind of input and target (route_jpeg.cpp, route_png.cpp,
-// route_webp.cpp, route_gif.cpp) and the pieces they share.  Every route takes the files of ONE kind as a batch of their own and answers per file: outputs zeroed and results
+// route_webp.cpp, route_gif.cpp, route_tiff.cpp) and the pieces they share.  Every route takes the files of ONE kind as a batch of their own and answers per file: outputs zeroed and results
 // success-initialised by the caller (for_subset), results never null, the number of failed files returned.
 #pragma once
 #include <vector>
@@ -24,6 +24,7 @@ int png_convert(const CByteArray *inputs, size_t count, const CCSParameters *p, 
 int rerun_to_size(const CByteArray *inputs, size_t count, const CCSParameters *p, size_t max_output_size, bool return_smallest, int device, CByteArray *outputs, CCSResult *results, bool webp);
 int webp_inputs(const CByteArray *inputs, size_t count, const CCSParameters *p, uint32_t target, int device, CByteArray *outputs, CCSResult *results);
 int gif_compress(const CByteArray *inputs, size_t count, const CCSParameters *p, int device, CByteArray *outputs, CCSResult *results, bool lossy);   // GIF -> GIF, the files CSH_GIF=device / lossy sends here
+int tiff_compress(const CByteArray *inputs, size_t count, const CCSParameters *p, int device, CByteArray *outputs, CCSResult *results, int compression);   // TIFF -> TIFF, the files CSH_TIFF sends here; compression: CST_OUT_*
 
 uint64_t webp_declared_pixels(const uint8_t *d, size_t n);   // capi.cpp, with cs_batch_extent
 // the alpha planes (grey pictures in device memory) of the lossy files outs[whose[j]]: the VP8L coder over them, each attached as an ALPH chunk (vp8l_encode.cpp).

@@ -42,6 +42,7 @@ enum {
     CS_ERR_BAD_PNG = 30100,        /* malformed / truncated PNG (chunk walk, zlib stream, filter bytes) */
     CS_ERR_BAD_WEBP = 40100,       /* malformed / truncated WebP (RIFF chunk walk, VP8 frame header, bool-coded data running out) */
     CS_ERR_BAD_GIF = 50100,        /* malformed / truncated GIF (block walk, a rectangle that leaves the canvas, LZW code size or codes, data that ends early); only under CSH_GIF=device */
+    CS_ERR_BAD_TIFF = 60100,       /* malformed / truncated TIFF (an offset or count outside the file, an IFD chain that loops, strip / tile arrays of the wrong length, a segment whose data is bad or ends early); only with CSH_TIFF set */
     CS_ERR_SAME_FORMAT = 10407,    /* convert_in_memory: source type == target type */
     CS_ERR_TOO_BIG = 10500         /* compress_to_size: cannot reach max_output_size */
 };
@@ -60,8 +61,9 @@ typedef struct {
     uint32_t gif_quality;
     uint32_t webp_quality;
     bool webp_lossless;
-    uint32_t tiff_compression;
-    uint32_t tiff_deflate_level;
+    uint32_t tiff_compression;        /* read under CSH_TIFF=device alone: 1 = LZW, 2 = Deflate, 3 = PackBits, anything else = uncompressed.  The numbering is libcaesium's C interface as
+                                         recalled -- libcaesium is not in this tree, so it is not pinned by a test against it */
+    uint32_t tiff_deflate_level;      /* not read: the TIFF route has no Deflate coder yet */
     uint32_t width;
     uint32_t height;
 } CCSParameters;
@@ -342,6 +344,42 @@ int csg_batch_read_canvas(csg_batch *b, size_t file, uint32_t frame, uint8_t *ds
    (l = 0), then the canonical indices of the table whose colour is within D of b's, by (distance squared, index), 63 at most; bytes behind count[b] are 0.
    A batch without a distance (D = 0) has no rows: every count is 1 */
 int csg_batch_read_near(csg_batch *b, size_t file, uint32_t frame, uint8_t *cand, uint8_t *count);
+
+/* ------------------------------------------------------------------------------------------------
+ * TIFF INPUTS (libcaesium: the tiff crate decodes and writes the file again with the compression asked for).  Built here: a lossless re-coder -- every strip or tile
+ * of every page is decoded on the device (uncompressed, LZW, Deflate, PackBits; horizontal predictor at 8 and 16 bits) and coded again as LZW, PackBits or
+ * uncompressed; samples are never interpreted except by the predictor, so every depth, photometric and palette travels as bytes.  DESIGN.md 8.4 states the output
+ * rule, the files that are passed through and the layout of the output byte for byte.
+ * cs_batch_compress and cs_batch_compress_to_size route TIFF files here when CSH_TIFF is in the environment, read on EVERY call: unset, empty or "pass" = the file
+ * is passed through as before; "device" = the output compression is p->tiff_compression (2, Deflate, answers CS_ERR_UNSUPPORTED: that coder is not built);
+ * "lzw" / "packbits" / "none" = that compression whatever the parameter says; any other value fails every TIFF of the call with CS_ERR_UNSUPPORTED and a message that
+ * names the variable.  A resize or a conversion from or to TIFF stays refused.  CSH_TIFF_STRIP (256..1048576, default 65536): the decoded bytes an output strip aims at.
+ * The coded file is returned even when it is larger than the input.
+ */
+typedef struct cst_batch cst_batch;
+enum { CST_NKERNELS = 11 };
+enum { CST_OUT_NONE = 0, CST_OUT_LZW = 1, CST_OUT_PACKBITS = 3 };   /* cst_batch_create's `compression`: tiff_compression's numbering */
+typedef struct {
+    float total_ms;                  /* hipEvent time from the first launch to the last, on the batch's stream */
+    float kernel_ms[CST_NKERNELS];   /* names: cst_kernel_name */
+    uint64_t in_bytes, out_bytes;    /* file bytes in and out, of the files the device coded */
+    uint32_t n_files, n_pages, n_segments;   /* (segments: of the output) */
+    uint32_t n_passed, n_failed;
+    uint32_t strip_bytes;            /* CSH_TIFF_STRIP as this batch read it */
+    uint32_t n_pred_won, n_pred_lost;   /* LZW pages coded both ways: Predictor 2 gave fewer bytes / did not */
+} cst_timing;
+const char *cst_kernel_name(int slot);
+/* inputs are borrowed until cst_batch_destroy */
+int cst_batch_create(const CByteArray *inputs, size_t count, const CCSParameters *p, int compression, int device, cst_batch **out);
+int cst_batch_run(cst_batch *b, cst_timing *t);
+int cst_batch_fetch(cst_batch *b, CByteArray *outputs, CCSResult *results);
+void cst_batch_destroy(cst_batch *b);
+/* stage taps for the tests.  cst_batch_pages: the file's code if it failed, -2 for a file that is passed through, else 0 with the page count.  cst_batch_page_info:
+   rowbytes and nsegments are the input's (a strip's or a tile's row; strips or tiles).  After cst_batch_run: cst_batch_read_decoded: the page's decoded bytes with
+   the predictor undone, the input's segments back to back (each rows x rowbytes) */
+int cst_batch_pages(cst_batch *b, size_t file, uint32_t *npages);
+int cst_batch_page_info(cst_batch *b, size_t file, uint32_t page, uint32_t *width, uint32_t *height, uint32_t *rowbytes, uint32_t *nsegments, uint32_t *tiled, uint64_t *decoded_bytes);
+int cst_batch_read_decoded(cst_batch *b, size_t file, uint32_t page, uint8_t *dst);
 
 #ifdef __cplusplus
 }
