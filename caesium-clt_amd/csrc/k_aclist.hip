@@ -701,11 +701,30 @@ __device__ __forceinline__ static uint32_t ref_step_tokens(const LV<uint32_t> (&
     }
     return tot;
 }
+// Pass 1 counts 17 symbols only -- (r << 4) | 1 for the sixteen runs and ZRL; the EOB runs are k_ac_runs' -- so the wave's histogram is 17 words a copy, not 256
+// (CSH_RH_WORDS: run r at word r, ZRL at word 16): 512 bytes a wave instead of 4 KB.  ref_hist_flush is hist_flush for that form: symbol (r << 4) | 1 is word 1 of
+// lane 4 r, ZRL word 0 of lane 60; every other symbol of the slot's row is written as zero, as before
+#define CSH_RH_WORDS 32
+__device__ __forceinline__ static void ref_hist_flush(uint32_t *hist, uint16_t *row, LV<uint32_t> (&freq)[4]) {
+    LFOR(l) {
+        uint32_t zrl = 0, run = 0;
+        CSH_UNROLL
+        for (int cpy = 0; cpy < 4; cpy++) {
+            uint32_t *h = hist + CSH_RH_WORDS * cpy;
+            if ((l & 3) == 0) { run += h[l >> 2]; h[l >> 2] = 0u; }
+            if (l == 60) { zrl += h[16]; h[16] = 0u; }
+        }
+        uint2 o; o.x = (zrl & 0xFFFFu) | (run << 16); o.y = 0u;
+        *reinterpret_cast<uint2 *>(row + 4 * l) = o;
+        freq[0][l] += zrl; freq[1][l] += run;
+    }
+}
 // TOKENS = false (CSH_REF_PACK, the default): the kernel stops after pass 1 -- it also stores every block's last N (lastn[], indexed like corr[]), and
 // k_list_refine_pack below derives the events again once the tables exist; no token, no reservation, no token region
 template <bool TOKENS>
-__global__ void __launch_bounds__(256, 5) k_list_refine(EncCtx c) {   // (five waves per SIMD: what its 32 KB of LDS per workgroup allow)
-    CSH_SHARED alignas(16) uint32_t s_hist[4][4][256];   // four copies, lane & 3 (k_list_stats)
+__global__ void __launch_bounds__(256, 6) k_list_refine(EncCtx c) {   // (six waves per SIMD asked for: <false> takes 65 VGPRs and holds seven, <true> 80 and six; 18 KB of LDS per workgroup
+                                                                      // would allow eight -- an eighth for <false>, at 64 VGPRs, measured no gain)
+    CSH_SHARED uint32_t s_hist[4][4][CSH_RH_WORDS];   // four copies, lane & 3 (k_list_stats); 17 words of each are used
     CSH_SHARED uint32_t s_lastn[4][256];     // per block: its last N, k << 6 | hex (0: no N)
     CSH_SHARED uint32_t s_nh[4][256];        // per block: its H entries
     CSH_SHARED uint32_t s_corr[4][256][2];   // per block: its correction word, high half first
@@ -722,10 +741,7 @@ __global__ void __launch_bounds__(256, 5) k_list_refine(EncCtx c) {   // (five w
     rg.base = 0; rg.cap = 0; rg.pad = 0;
     if (TOKENS) rg = c.regions[r.region];
     uint32_t *hist = &s_hist[wv][0][0], *lastn = s_lastn[wv], *nh = s_nh[wv], *corr = &s_corr[wv][0][0];
-    LFOR(l) {   // (a chunk's flush leaves it at zero for the next)
-        uint4 zero; zero.x = zero.y = zero.z = zero.w = 0u;
-        for (int i = 4 * l; i < 1024; i += 256) *reinterpret_cast<uint4 *>(hist + i) = zero;
-    }
+    LFOR(l) for (int i = l; i < 4 * CSH_RH_WORDS; i += 64) hist[i] = 0u;   // (a chunk's flush leaves it at zero for the next)
     const uint32_t Ss = r.Ss, Se = r.Se;
     LV<uint32_t> freq[4];   // the run's count of symbols 4 l .. 4 l + 3 (k_list_stats)
     LFOR(l) { freq[0][l] = 0u; freq[1][l] = 0u; freq[2][l] = 0u; freq[3][l] = 0u; }
@@ -752,7 +768,7 @@ __global__ void __launch_bounds__(256, 5) k_list_refine(EncCtx c) {   // (five w
             if (g0 + 256u < ls.n) LFOR(l) list_load4(ls, g0 + 256u + 4u * uint32_t(l), x[0][l], x[1][l], x[2][l], x[3][l]);
             ref_step<false>(e, Ss, Se, C, hex, z, zp, zq);
             LFOR(l) {
-                uint32_t *h = hist + 256 * (l & 3);
+                uint32_t *h = hist + CSH_RH_WORDS * (l & 3);
                 CSH_UNROLL
                 for (int q = 0; q < 4; q++) {
                     const uint32_t v = e[q][l], blk = (v >> 23) & 255u;
@@ -762,8 +778,8 @@ __global__ void __launch_bounds__(256, 5) k_list_refine(EncCtx c) {   // (five w
                     } else if (ref_isN(v, Ss, Se)) {
                         const uint32_t zr = z[q][l] - zp[q][l];
                         atomicMax(&lastn[blk], ((v & 127u) << 6) | hex[q][l]);
-                        atomicAdd(&h[((zr & 15u) << 4) | 1u], 1u);
-                        if (zr >> 4) atomicAdd(&h[0xF0], zr >> 4);
+                        atomicAdd(&h[zr & 15u], 1u);            // symbol (zr & 15) << 4 | 1
+                        if (zr >> 4) atomicAdd(&h[16], zr >> 4);   // ZRL
                         ntok[l] += 1u + (zr >> 4);
                     }
                 }
@@ -788,7 +804,7 @@ __global__ void __launch_bounds__(256, 5) k_list_refine(EncCtx c) {   // (five w
             LFOR(l) if (l == 0 && j * 4u + w4 < ((r.nunits_work + 63u) >> 6)) { c.sym_bits[r.word_base + j * 4u + w4] = ms; c.eob_bits[r.word_base + j * 4u + w4] = me; }
         }
         const uint32_t total = lsum32(ntok);
-        hist_flush(hist, c.slot_hist + size_t(hist_row) * 256u, freq);
+        ref_hist_flush(hist, c.slot_hist + size_t(hist_row) * 256u, freq);
         LFOR(l) if (l == 0) c.slot_raw[cs] = C.runN + C.runH;   // a sign bit per new coefficient, a correction bit per old one
         if (c.stats_only || !TOKENS) continue;   // (nothing is written to the pool)
         // ---- room in the pool: one atomic add on the region's cursor
@@ -829,18 +845,21 @@ __global__ void __launch_bounds__(256, 5) k_list_refine(EncCtx c) {   // (five w
 // entry's correction bit rides behind the block's next token): the tokens are the dense form of the step, and the bit work is done on them, not per entry.
 // Tokens of a step.  Per block: one per N entry, at most 3 ZRLs (z <= 62), one EOB -- at most N + 4 for at least N + 1 entries (its END), and N + 4 > N + 1
 // needs an N: at least 2 entries.  So a block inside the step has at most 2.5 tokens per entry, the two blocks cut by the step's edges at most 3 + 1 more
-// than their entries: 256 x 2.5 + 8 = 648 tokens at most; the buffer holds 704.
+// than their entries: 256 x 2.5 + 8 = 648 tokens at most (CSH_RP_STEP_TOKENS).  The buffer holds a ROUND of 256 of them: a step with more -- ZRLs must outnumber
+// its H entries for that, which pictures seldom do -- is derived again, from the carries it started with and its entries out of the L2, once per further round,
+// and ref_step_tokens keeps the round's tokens only (its `at` is minus the round's first token: the others fall outside `limit`).  At most three rounds a step.
 // Bits of a sub-step.  A token emits a symbol of at most 16 bits and a sign bit or at most 14 run bits, then at most 63 correction bits: 30 + 63 = 93 bits --
 // 3 ZRLs, a symbol, a sign bit and 63 correction bits of one entry are 4 of these tokens.  A sub-step is 64 tokens, one per lane: 64 x 93 = 5 952 bits = 186
-// words.  (Small on purpose: the kernel waits on its chain of wave scans, so what counts is how many waves a SIMD holds, and LDS decides that -- 8 KB a wave,
-// 32 KB a workgroup, five workgroups per CU, as k_list_refine.)
-#define CSH_RP_TOKENS 704   // the wave's token buffer, in LDS words (a step of 256 entries makes at most 648 tokens, see above)
+// words.  (Small on purpose: the kernel waits on its chain of wave scans, so what counts is how many waves a SIMD holds, and LDS decides that -- 5.4 KB a wave
+// with the 32-code table of tok_bits.h and the round of 256 tokens, 21.5 KB a workgroup, seven workgroups per CU.)
+#define CSH_RP_STEP_TOKENS 648   // a step of 256 entries makes at most this many tokens (see above)
+#define CSH_RP_TOKENS 256   // the wave's token buffer, in LDS words: one round of a step's tokens
 #define CSH_RP_SUB 64       // tokens per sub-step
 #define CSH_RP_WORDS 256    // the window of the bit stream, per wave, in LDS words (a sub-step of 64 tokens adds at most 186, see above)
 #define CSH_RP_STEP 192     // slide when fewer words than this are left behind the complete ones: 1 partial word + 186 + the word lor_bits may touch behind its own
-__global__ void __launch_bounds__(256, 5) k_list_refine_pack(EncCtx c) {   // (five waves per SIMD: what its 32 KB of LDS per workgroup allow)
+__global__ void __launch_bounds__(256, 7) k_list_refine_pack(EncCtx c) {   // (seven waves per SIMD: what its 21.5 KB of LDS per workgroup allow)
     CSH_SHARED alignas(16) uint32_t s_win[4][CSH_RP_WORDS];
-    CSH_SHARED uint32_t s_lut[4][256];
+    CSH_SHARED uint32_t s_lut[4][CSH_REF_CODES];
     CSH_SHARED uint64_t s_corr[4][256];
     CSH_SHARED uint16_t s_eob[4][256];
     CSH_SHARED uint16_t s_lastn[4][256];   // per block: its last N, k << 6 | hex (0: no N)
@@ -868,13 +887,13 @@ __global__ void __launch_bounds__(256, 5) k_list_refine_pack(EncCtx c) {   // (f
     uint8_t *nh = s_nh[wv];
     uint32_t *tok = s_tok[wv];
     LFOR(l) {
-        for (int i = l; i < 256; i += 64) lut[i] = c.tables[r.table_base].lut[i];
+        if (l < CSH_REF_CODES) lut[l] = c.tables[r.table_base].lut[((uint32_t(l) & 15u) << 4) | (uint32_t(l) >> 4)];   // the symbol whose ref_code_index is l
         uint4 zero; zero.x = zero.y = zero.z = zero.w = 0u;
         for (int i = 4 * l; i < CSH_RP_WORDS; i += 256) *reinterpret_cast<uint4 *>(buf + i) = zero;
     }
     CSP_WAVE_SYNC();
     TokenCtx x;   // the chunk's, out of LDS
-    x.lut = lut; x.lut_stride = 256; x.eobrun = eobrun; x.corr = corr;
+    x.lut = lut; x.lut_stride = CSH_REF_CODES; x.eobrun = eobrun; x.corr = corr;   // (the 32-code table: token_main / token_pieces <2, true>)
     uint32_t *out = c.raw + (raw_bit0 >> 5);        // word 0 of the frame below
     uint64_t pos = raw_bit0 & 31u;                   // next bit, in the frame whose word 0 is the run's first word in the pool
     uint32_t ww = 0;                                 // first word of the window
@@ -909,31 +928,40 @@ __global__ void __launch_bounds__(256, 5) k_list_refine_pack(EncCtx c) {   // (f
         C.runH = C.runN = C.base = C.prevN = C.prevNZ = 0u;
         uint32_t curc = 0;
         for (uint32_t g0 = 0; g0 < ls.n; g0 += 256) {
+            const RefCarry C0 = C;   // what the step starts with: a further round derives it again from here
+            const uint32_t curc0 = curc;
+            for (uint32_t t0 = 0;; t0 += CSH_RP_TOKENS) {   // the rounds: tokens t0 .. t0 + CSH_RP_TOKENS - 1 of the step (one round, but for a step of many ZRLs)
             uint32_t ntok;
             {
                 LV<uint32_t> e[4], hex[4], z[4], zp[4], zq[4];
-                LFOR(l) { e[0][l] = xn[0][l]; e[1][l] = xn[1][l]; e[2][l] = xn[2][l]; e[3][l] = xn[3][l]; }
-                if (g0 + 256u < ls.n) LFOR(l) list_load4(ls, g0 + 256u + 4u * uint32_t(l), xn[0][l], xn[1][l], xn[2][l], xn[3][l]);
+                if (t0 == 0u) {
+                    LFOR(l) { e[0][l] = xn[0][l]; e[1][l] = xn[1][l]; e[2][l] = xn[2][l]; e[3][l] = xn[3][l]; }
+                    if (g0 + 256u < ls.n) LFOR(l) list_load4(ls, g0 + 256u + 4u * uint32_t(l), xn[0][l], xn[1][l], xn[2][l], xn[3][l]);
+                } else {
+                    C = C0; curc = curc0;
+                    LFOR(l) list_load4(ls, g0 + 4u * uint32_t(l), e[0][l], e[1][l], e[2][l], e[3][l]);
+                }
                 ref_step<true>(e, Ss, Se, C, hex, z, zp, zq);
-                ntok = ref_step_tokens(e, hex, z, zp, zq, Ss, Se, lastn, nh, curc, tok, 0u, uint32_t(CSH_RP_TOKENS));
+                ntok = ref_step_tokens(e, hex, z, zp, zq, Ss, Se, lastn, nh, curc, tok, 0u - t0, uint32_t(CSH_RP_TOKENS));
             }
 #ifdef CSH_EMUL
-            if (ntok > CSH_RP_TOKENS) { fprintf(stderr, "k_list_refine_pack: a step of %u tokens\n", ntok); abort(); }
+            if (ntok > CSH_RP_STEP_TOKENS) { fprintf(stderr, "k_list_refine_pack: a step of %u tokens\n", ntok); abort(); }
 #endif
             CSP_WAVE_SYNC();
-            // the step's tokens, 64 at a time, one per lane: the one-piece form first, the three pieces for the whole sub-step where a lane needs them
-            for (uint32_t s0 = 0; s0 < ntok; s0 += CSH_RP_SUB) {
+            // the round's tokens, 64 at a time, one per lane: the one-piece form first, the three pieces for the whole sub-step where a lane needs them
+            const uint32_t nround = ntok - t0 < uint32_t(CSH_RP_TOKENS) ? ntok - t0 : uint32_t(CSH_RP_TOKENS);
+            for (uint32_t s0 = 0; s0 < nround; s0 += CSH_RP_SUB) {
                 LV<uint32_t> t, pv[3], pn[3], slow, len;
                 LFOR(l) {
                     const uint32_t i = s0 + uint32_t(l);
-                    t[l] = i < ntok ? tok[i] : uint32_t(TK_RAW);   // (an empty RAW token emits nothing)
+                    t[l] = i < nround ? tok[i] : uint32_t(TK_RAW);   // (an empty RAW token emits nothing)
                     uint32_t v, n;
-                    slow[l] = token_main<2>(t[l], x, v, n) ? 0u : 1u;
+                    slow[l] = token_main<2, true>(t[l], x, v, n) ? 0u : 1u;
                     pv[0][l] = v; pn[0][l] = n; pv[1][l] = 0u; pn[1][l] = 0u; pv[2][l] = 0u; pn[2][l] = 0u;
                 }
                 if (lballot([&](int b) { return slow[b] != 0u; })) {
                     LFOR(l) {
-                        const Pieces p = token_pieces<2>(t[l], x);
+                        const Pieces p = token_pieces<2, true>(t[l], x);
                         CSH_UNROLL
                         for (int k = 0; k < 3; k++) { pv[k][l] = p.v[k]; pn[k][l] = p.n[k]; }
                     }
@@ -962,7 +990,9 @@ __global__ void __launch_bounds__(256, 5) k_list_refine_pack(EncCtx c) {   // (f
                     ww += done; first_flush = false;
                 }
             }
-            CSP_WAVE_SYNC();   // (the next step writes its tokens over these)
+            CSP_WAVE_SYNC();   // (the next round or step writes its tokens over these)
+            if (t0 + uint32_t(CSH_RP_TOKENS) >= ntok) break;
+            }
         }
     }
     // the byte fill of the scan's last chunk, behind the run's last token (the window has room for a sub-step, and the window is zero behind `pos`)

@@ -451,7 +451,8 @@ __global__ void __launch_bounds__(64) k_trellis_dc(TrellisCtx c) {
         int qprev = 0, sprev = 0;   // the block before: its rounded level and sign
         bool cprev_clamped = false;
         // a lane walks its row block by block and every step needs that block's record: the next one is fetched a step ahead (the walk
-        // was bound by the latency of these loads: 6 waves per SIMD, two dependent loads per block)
+        // was bound by the latency of these loads, two dependent loads per block, when it ran at 6 waves per SIMD; since its per-level tests were unrolled away the
+        // kernel takes 204 VGPRs and holds 2 waves per SIMD: profiles/residency_resources.txt)
         uint64_t rec_next = c.dcrec[w.unit_base + uint32_t(by * g.real_bw)];
         for (int bi = 0; bi < g.real_bw; bi++) {
             const uint32_t u = uint32_t(by * g.real_bw + bi);
