@@ -55,6 +55,8 @@ struct DecodePlan {
     bool clear_front = false;                               // PlanSwitches::dec_clear_front: a memset in front of the phase clears the tiles, no decoding pass does (measurements)
     std::vector<uint32_t> h_relax_cnt;                      // the host's copy of d_relax_cnt (the read-backs between the list rounds)
     uint32_t last_run_seeds = 0, last_run_relaxed = 0;      // csh_timing.n_dec_seeds / n_dec_relaxed of the last run
+    int test_rounds = -1;                                   // PlanSwitches::test_dec_rounds: the list rounds stop there (-1: at the length of d_relax_cnt)
+    uint32_t last_run_rounds = 0;                           // csh_timing.n_dec_rounds of the last run
     DevBuf<uint32_t> d_seed_cnt;
     DevBuf<uint64_t> d_seed_off;
 
@@ -336,6 +338,7 @@ struct PlanSwitches {
     bool ac_tiles = false;      // CSH_AC_TILES == "1": every component's AC levels are stored to its tiles, as before they lived in the lists
     uint32_t dec_group = 0;     // CSH_DEC_GROUP: 1, 2, 4 or 8 (DecodePlan::group); 0 for anything else: the planner chooses by the batch's size
     bool dec_clear_front = false;   // CSH_DEC_CLEAR == "front": the tiles and the EOBRUN array are cleared by memsets, not behind the speculation pass's work (what the clearing costs there: DESIGN 10)
+    int test_dec_rounds = -1;   // CSH_TEST_DEC_ROUNDS=n (tests): at most n list rounds, so that small inputs reach k_dec_chain and the sequential kernel's hand-over; -1 when unset
     uint32_t dec_lanes = 0;     // CSH_DEC_LANES: 192 or 256 lanes a workgroup of k_dec_spec_group; 0 for anything else: the default
     static PlanSwitches read();
 };

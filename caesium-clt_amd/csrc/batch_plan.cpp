@@ -254,6 +254,7 @@ PlanSwitches PlanSwitches::read() {
     s.ac_runs_slot = is("CSH_AC_RUNS", "slot");
     for (uint32_t g : {1u, 2u, 4u, 8u}) if (is("CSH_DEC_GROUP", std::to_string(g).c_str())) s.dec_group = g;
     s.dec_clear_front = is("CSH_DEC_CLEAR", "front");
+    if (const char *tr = getenv("CSH_TEST_DEC_ROUNDS")) { if (*tr) s.test_dec_rounds = std::max(0, atoi(tr)); }   // (an unsupported test hook, like CSH_TEST_POOL_SHIFT)
     s.dec_lanes = is("CSH_DEC_LANES", "192") ? 192u : is("CSH_DEC_LANES", "256") ? 256u : 0u;
     return s;
 }
@@ -1226,6 +1227,7 @@ int BatchPlanner::upload(Laps &laps) {
     if (!b->nimg) return 0;
     b->dec.bits_pool.flush_copies();
     laps.lap("copy_in");
+    b->dec.need_seq_init.resize(size_t(b->nimg) + CSH_DEC_NSTATS, 0u);   // behind the images' words: the decoder's counters (kernels.h), zero in front of every run by the copy that resets need_seq
     if (b->dec.d_bits.alloc(b->dec.bits_pool.size()) || (b->dec.bits_pool.size() && hipMemcpyAsync(b->dec.d_bits.p, b->dec.bits_pool.p, b->dec.bits_pool.size(), hipMemcpyHostToDevice, st) != hipSuccess) ||
         b->d_imgs.upload(b->imgs, st) || b->dec.d_dscans.upload(b->dec.dscans, st) || b->dec.d_chains.upload(b->dec.chains, st) || b->dec.d_chain_scans.upload(b->dec.chain_scans, st) ||
         b->dec.d_hsets.upload(b->dec.hsets, st) || b->dec.d_phsets.upload(b->dec.phsets, st) || (b->dec.use4 && b->dec.d_phsets4.upload(b->dec.phsets4, st)) || b->d_quants.upload(b->quants, st) || b->pix.d_pwork.upload(b->pix.pwork, st) ||
@@ -1237,10 +1239,11 @@ int BatchPlanner::upload(Laps &laps) {
     b->dec.group = sw.dec_group ? sw.dec_group : dec_group_for(b->dec.total_sub);
     b->dec.spec_lanes = sw.dec_lanes ? sw.dec_lanes : kDecSpecLanes;
     b->dec.clear_front = sw.dec_clear_front;
+    b->dec.test_rounds = sw.test_dec_rounds;
     if (b->dec.d_seed_cnt.alloc(b->dec.pscans.size() + 1) || b->dec.d_seed_off.alloc(b->dec.pscans.size() + 2)) return CS_ERR_NO_DEVICE;
     if (b->dec.d_clean.alloc(b->dec.bits_pool.size() + 64) || b->dec.d_unstuff_cnt.alloc(nchunks + 1) || b->dec.d_unstuff_off.alloc(nchunks + 2) ||
         b->dec.d_pstate.alloc(nst) || b->dec.d_relax_list[0].alloc(nst) || b->dec.d_relax_list[1].alloc(nst) || b->dec.d_relax_cnt.alloc(512) || b->dec.d_scan_pending.alloc(b->dec.pscans.size() + 1) || b->dec.d_cut_block.alloc(b->dec.pscans.size() + 1) || b->dec.d_claim.alloc(size_t(b->dec.total_sub) + 1) || b->dec.d_hyp.alloc((size_t(b->dec.total_sub) + 1) * 10) ||
-        b->dec.d_nblk.alloc(size_t(b->dec.total_sub) + 1) || b->dec.d_blk_off.alloc(size_t(b->dec.total_sub) + 2) || b->dec.d_need_seq.alloc(b->nimg + 1) ||
+        b->dec.d_nblk.alloc(size_t(b->dec.total_sub) + 1) || b->dec.d_blk_off.alloc(size_t(b->dec.total_sub) + 2) || b->dec.d_need_seq.alloc(size_t(b->nimg) + CSH_DEC_NSTATS + 1) ||
         b->dec.d_dcdiff.alloc(size_t(b->dec.dc_total) + 1) || b->dec.d_dc_off.alloc(size_t(b->dec.dc_total) + 2) ||
         b->dec.d_refine_hist.alloc(size_t(b->dec.refine_hist) + 1) || b->dec.d_refine_pos.alloc(size_t(b->dec.refine_pos) + 1) || b->dec.d_refine_units.upload(b->dec.refine_units, st) ||
         b->dec.d_refine_prog.alloc(b->dec.refine_units.size() + 1))

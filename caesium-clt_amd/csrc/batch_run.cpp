@@ -111,7 +111,7 @@ struct Run {
         const bool spec = !b->dec.pscans.empty() && b->dec.max_sub != 0, zero_in_spec = spec && !b->dec.clear_front;
         if (!zero_in_spec) CSH_CHECK(hipMemsetAsync(b->d_coef.p, 0, size_t(b->ntiles_in) * CSH_TILE_I16 * sizeof(int16_t), st));
         if (b->out.d_status.zero(st) || b->out.d_overflow.zero(st)) return -1;
-        CSH_CHECK(hipMemcpyAsync(b->dec.d_need_seq.p, b->dec.d_need_seq_init.p, size_t(nimg) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        CSH_CHECK(hipMemcpyAsync(b->dec.d_need_seq.p, b->dec.d_need_seq_init.p, (size_t(nimg) + CSH_DEC_NSTATS) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));   // (and the counters behind them: zero)
         MARK(KS_MEMSET_COEF);
         {   // parallel self-synchronising decode of sequential-mode scans
             int nps = int(b->dec.pscans.size());
@@ -132,6 +132,7 @@ struct Run {
             const uint64_t eob_all = (uint64_t(b->enc.d_eobrun.n) * sizeof(uint16_t)) & ~uint64_t(15), eob_half = (eob_all / 2) & ~uint64_t(15);   // (the last < 16 bytes: a memset below)
             da.live_cnt = b->dec.d_relax_cnt.p + b->dec.d_relax_cnt.n - 1; da.seed_cnt = b->dec.d_seed_cnt.p;   // (the last count: no round's)
             const uint32_t G = spec ? b->dec.group : 1u;   // (nothing to speculate on: every launch below does nothing)
+            uint32_t *const dec_stats = b->dec.d_need_seq.p + nimg;   // (kernels.h CSH_DEC_STAT_*)
             const int seam = G > 1 ? 1 : 0;                        // the seam round takes list 0 / count 0: list round R then reads list (R + seam) & 1 and count R + seam
             const uint64_t eob_tail = uint64_t(b->enc.d_eobrun.n) * sizeof(uint16_t) - eob_all;
             if (G > 1) {
@@ -150,7 +151,7 @@ struct Run {
                 launch_exclusive_scan(st, b->dec.d_seed_cnt.p, b->dec.d_seed_off.p, uint64_t(nps), b->enc.d_scan_tmp.p, b->enc.d_scan_tmp.n);
                 launch_dec_seed(st, b->dec.d_seed_off.p, nps, b->dec.max_sub, G, b->dec.d_relax_list[0].p, b->dec.d_relax_cnt.p);
                 launch_dec_relax_list(st, b->dec.d_clean.p, b->dec.d_pscans.p, b->dec.total_sub, da.huffs, da.compact, b->dec.d_pstate.p, b->dec.d_nblk.p, b->dec.d_relax_list[0].p,
-                                      b->dec.d_relax_cnt.p, b->dec.d_relax_list[1].p, b->dec.d_relax_cnt.p + 1, b->dec.d_pstate.n, b->dec.d_claim.p, 0x80000000u, false);
+                                      b->dec.d_relax_cnt.p, b->dec.d_relax_list[1].p, b->dec.d_relax_cnt.p + 1, b->dec.d_pstate.n, b->dec.d_claim.p, 0x80000000u, dec_stats, false);
                 MARK(KS_DEC_RELAX0);
             } else {
                 if (zero_in_spec) { da.zero_ptr = reinterpret_cast<uint8_t *>(b->d_coef.p); da.zero_bytes = zero_half; da.zero2_ptr = reinterpret_cast<uint8_t *>(b->enc.d_eobrun.p); da.zero2_bytes = eob_half; }
@@ -174,19 +175,26 @@ struct Run {
             // wrong state then survives most of the cuts it crosses) -- so the host looks at the list length after 12 rounds and
             // then after every 8 (a read-back of the counts; an empty round is a ~6 us launch), up to kMaxRounds.  What is still listed
             // after that goes through the label chain below or to the sequential kernel.
-            const int kMaxRounds = int(b->dec.d_relax_cnt.n) - 2 - seam;   // (the last count is DenseArgs::live_cnt)
+            // (CSH_TEST_DEC_ROUNDS, for the tests: fewer rounds, so that small files are still listed behind them)
+            const int kAllRounds = int(b->dec.d_relax_cnt.n) - 2 - seam;   // (the last count is DenseArgs::live_cnt)
+            const int kMaxRounds = b->dec.test_rounds >= 0 ? std::min(b->dec.test_rounds, kAllRounds) : kAllRounds;
             std::vector<uint32_t> &cnt = b->dec.h_relax_cnt;
             cnt.assign(b->dec.d_relax_cnt.n, 0u);
             int R = 0;
             for (int group = 12; nps && R < kMaxRounds; group = 8) {
                 for (int g = 0; g < group && R < kMaxRounds; g++, R++)
                     launch_dec_relax_list(st, b->dec.d_clean.p, b->dec.d_pscans.p, b->dec.total_sub, da.huffs, da.compact, b->dec.d_pstate.p, b->dec.d_nblk.p, b->dec.d_relax_list[(R + seam) & 1].p,
-                                          b->dec.d_relax_cnt.p + R + seam, b->dec.d_relax_list[((R + seam) & 1) ^ 1].p, b->dec.d_relax_cnt.p + R + seam + 1, b->dec.d_pstate.n, b->dec.d_claim.p, uint32_t(R + 1));
+                                          b->dec.d_relax_cnt.p + R + seam, b->dec.d_relax_list[((R + seam) & 1) ^ 1].p, b->dec.d_relax_cnt.p + R + seam + 1, b->dec.d_pstate.n, b->dec.d_claim.p, uint32_t(R + 1), dec_stats);
                 // (the whole array, 2 KB: the counts in front of the last one are csh_timing's n_dec_seeds and n_dec_relaxed)
                 CSH_CHECK(hipMemcpyAsync(cnt.data(), b->dec.d_relax_cnt.p, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
                 CSH_CHECK(hipStreamSynchronize(st));
                 if (!cnt[size_t(R + seam)]) break;
             }
+            if (nps && !R) {   // (no round at all: the counts of the passes in front of them)
+                CSH_CHECK(hipMemcpyAsync(cnt.data(), b->dec.d_relax_cnt.p, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+                CSH_CHECK(hipStreamSynchronize(st));
+            }
+            b->dec.last_run_rounds = uint32_t(R);
             b->dec.last_run_seeds = cnt[0];
             b->dec.last_run_relaxed = cnt.back();   // (G = 1: what the dense relaxation pass evaluated)
             for (int r = 0; r < R + seam; r++) b->dec.last_run_relaxed += cnt[size_t(r)];
@@ -195,7 +203,7 @@ struct Run {
                 launch_dec_mark_pending(st, b->dec.d_pscans.p, b->dec.total_sub, b->dec.d_relax_list[(R + seam) & 1].p, b->dec.d_relax_cnt.p + R + seam, b->dec.d_scan_pending.p);
                 da.hyp = b->dec.d_hyp.p; da.scan_pending = b->dec.d_scan_pending.p;
                 launch_dec_dense(st, 3, nps, b->dec.max_sub, da);
-                launch_dec_chain(st, b->dec.d_pscans.p, nps, b->dec.d_pstate.p, b->dec.d_nblk.p, b->dec.d_hyp.p, b->dec.d_scan_pending.p, b->dec.d_need_seq.p);
+                launch_dec_chain(st, b->dec.d_pscans.p, nps, b->dec.d_pstate.p, b->dec.d_nblk.p, b->dec.d_hyp.p, b->dec.d_scan_pending.p, b->dec.d_need_seq.p, dec_stats);
             }
             MARK(KS_DEC_RELAX);
             if (nps) launch_exclusive_scan(st, b->dec.d_nblk.p, b->dec.d_blk_off.p, b->dec.total_sub, b->enc.d_scan_tmp.p, b->enc.d_scan_tmp.n);
@@ -485,7 +493,7 @@ struct Run {
 int run_once(csh_batch *b, csh_timing *t, bool requant_only) {
     Run r(b, t);
     b->enc.last_run_list_runs = 0;
-    b->dec.last_run_seeds = 0; b->dec.last_run_relaxed = 0;   // (a run that does not decode reports none)
+    b->dec.last_run_seeds = 0; b->dec.last_run_relaxed = 0; b->dec.last_run_rounds = 0;   // (a run that does not decode reports none)
     b->enc.last_run_fused = 0; b->enc.last_run_refine = 0; b->enc.last_run_ref_packed = 0; b->enc.last_run_ac_lists = 0;
     if (r.pools() || r.marks.start()) return -1;
     // a re-run at another quality (size targeting): from the retained DCT -- unless the batch derings: the overshoot mozjpeg's deringing allows

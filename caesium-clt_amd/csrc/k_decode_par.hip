@@ -414,7 +414,7 @@ __device__ __forceinline__ static bool par_decoded(int kind) { return kind == CS
 template <class SET>
 __global__ void __launch_bounds__(CSH_LIST_LANES) k_dec_relax_list(const uint8_t *clean, const ParScan *pss, const SET *huffs, uint64_t *state, const uint64_t *state_rd,
                                                          uint32_t *nblk, const uint64_t *list_in, const uint32_t *cnt_in, uint64_t *list_out, uint32_t *cnt_out,
-                                                         uint32_t *claim, uint32_t epoch, uint32_t walk_below) {
+                                                         uint32_t *claim, uint32_t epoch, uint32_t walk_below, uint32_t *stats) {
     CSH_SHARED uint32_t lbits[CSH_LIST_LANES * CSH_LROW_STRIDE];
     CSH_SHARED SET lhs;
     CSH_SHARED uint32_t d_scan[CSH_LIST_LANES], d_t[CSH_LIST_LANES];   // per lane: ParScan index (0xFFFFFFFF = idle), sub-sequence
@@ -467,6 +467,7 @@ __global__ void __launch_bounds__(CSH_LIST_LANES) k_dec_relax_list(const uint8_t
             if ((t + 1) * CSH_SUBSEQ_BYTES >= ps.clean_len) break;          // past the data
             if (count < walk_below && step + 1 < CSH_LIST_WALK && atomicExch(&claim[ps.sub_base + t + 1], epoch) != epoch) {
                 t++;                                                         // walk on: this lane's own row is refilled by the lane itself
+                atomicAdd(&stats[CSH_DEC_STAT_WALKED], 1u);
                 for (uint32_t i = 0; i < CSH_LROW_WORDS; i++) row[i] = g.word(t * (CSH_SUBSEQ_BYTES / 4) + i);
                 continue;
             }
@@ -487,11 +488,12 @@ __global__ void __launch_bounds__(256) k_dec_mark_pending(const ParScan *pss, co
     if (j >= *cnt_in) return;
     scan_pending[uint32_t(list_in[j] >> 32)] = 1;
 }
-__global__ void k_dec_chain(const ParScan *pss, int nps, uint64_t *state, uint32_t *nblk, const uint16_t *hyp, const uint32_t *scan_pending, uint32_t *need_seq) {
+__global__ void k_dec_chain(const ParScan *pss, int nps, uint64_t *state, uint32_t *nblk, const uint16_t *hyp, const uint32_t *scan_pending, uint32_t *need_seq, uint32_t *stats) {
     int si = blockIdx.x * blockDim.x + threadIdx.x;
     if (si >= nps || !scan_pending[si] || !par_decoded(pss[si].kind)) return;
     const ParScan &ps = pss[si];
-    if (ps.kind == CSH_PS_AC_FIRST) { need_seq[ps.image] = 2; return; }   // (no label to settle there: a scan still listed is not converging -- the sequential kernel takes the image)
+    atomicAdd(&stats[CSH_DEC_STAT_CHAIN_SCANS], 1u);
+    if (ps.kind == CSH_PS_AC_FIRST) { atomicAdd(&stats[CSH_DEC_STAT_CHAIN_FAILED], 1u); need_seq[ps.image] = 2; return; }   // (no label to settle there: a scan still listed is not converging -- the sequential kernel takes the image)
     uint32_t nsub = (ps.bits_len + CSH_SUBSEQ_BYTES - 1) / CSH_SUBSEQ_BYTES;
     size_t base = ps.sub_base + ps.par_index;
     int m = 0;
@@ -500,7 +502,7 @@ __global__ void k_dec_chain(const ParScan *pss, int nps, uint64_t *state, uint32
         st.m = m;
         state[base + t] = pack_state(st);
         uint16_t h = hyp[(size_t(ps.sub_base) + t) * 10 + m];
-        if (h == 0xFFFF) { need_seq[ps.image] = 2; return; }
+        if (h == 0xFFFF) { atomicAdd(&stats[CSH_DEC_STAT_CHAIN_FAILED], 1u); need_seq[ps.image] = 2; return; }
         nblk[ps.sub_base + t] = h & 4095u;
         m = h >> 12;
     }
@@ -793,7 +795,7 @@ void launch_dec_seed(hipStream_t st, const uint64_t *seed_off, int nps, uint32_t
 int csh_emul_jacobi = 0;  // tests: make a list round read the states as they were BEFORE the launch (what concurrent lanes see at worst)
 #endif
 void launch_dec_relax_list(hipStream_t st, const uint8_t *clean, const ParScan *ps, uint32_t total_sub, const void *huffs, int compact, uint64_t *state, uint32_t *nblk,
-                           const uint64_t *list_in, const uint32_t *cnt_in, uint64_t *list_out, uint32_t *cnt_out, size_t nstate, uint32_t *claim, uint32_t epoch, bool walk) {
+                           const uint64_t *list_in, const uint32_t *cnt_in, uint64_t *list_out, uint32_t *cnt_out, size_t nstate, uint32_t *claim, uint32_t epoch, uint32_t *stats, bool walk) {
     // walking starts when the list is down to 0.1 % of the sub-sequences, or after ten launches whatever its size: files of
     // ordinary quality are through by then (their lists shrink by 60 % a launch and walking would only make their waves wait
     // for the walkers), what is left is slow-to-synchronise data that needs it
@@ -807,8 +809,8 @@ void launch_dec_relax_list(hipStream_t st, const uint8_t *clean, const ParScan *
 #else
     (void)nstate;
 #endif
-    if (compact) CSH_LAUNCH_PHASED(k_dec_relax_list<ParHuffSet4>, 3, dim3((total_sub + CSH_LIST_LANES - 1) / CSH_LIST_LANES), dim3(CSH_LIST_LANES), st, clean, ps, static_cast<const ParHuffSet4 *>(huffs), state, state_rd, nblk, list_in, cnt_in, list_out, cnt_out, claim, epoch, walk_below);
-    else CSH_LAUNCH_PHASED(k_dec_relax_list<ParHuffSet>, 3, dim3((total_sub + CSH_LIST_LANES - 1) / CSH_LIST_LANES), dim3(CSH_LIST_LANES), st, clean, ps, static_cast<const ParHuffSet *>(huffs), state, state_rd, nblk, list_in, cnt_in, list_out, cnt_out, claim, epoch, walk_below);
+    if (compact) CSH_LAUNCH_PHASED(k_dec_relax_list<ParHuffSet4>, 3, dim3((total_sub + CSH_LIST_LANES - 1) / CSH_LIST_LANES), dim3(CSH_LIST_LANES), st, clean, ps, static_cast<const ParHuffSet4 *>(huffs), state, state_rd, nblk, list_in, cnt_in, list_out, cnt_out, claim, epoch, walk_below, stats);
+    else CSH_LAUNCH_PHASED(k_dec_relax_list<ParHuffSet>, 3, dim3((total_sub + CSH_LIST_LANES - 1) / CSH_LIST_LANES), dim3(CSH_LIST_LANES), st, clean, ps, static_cast<const ParHuffSet *>(huffs), state, state_rd, nblk, list_in, cnt_in, list_out, cnt_out, claim, epoch, walk_below, stats);
 #ifdef CSH_EMUL
     free(snap);
 #endif
@@ -816,8 +818,8 @@ void launch_dec_relax_list(hipStream_t st, const uint8_t *clean, const ParScan *
 void launch_dec_mark_pending(hipStream_t st, const ParScan *ps, uint32_t total_sub, const uint64_t *list_in, const uint32_t *cnt_in, uint32_t *scan_pending) {
     if (total_sub) CSH_LAUNCH(k_dec_mark_pending, dim3((total_sub + 255) / 256), dim3(256), st, ps, list_in, cnt_in, scan_pending);
 }
-void launch_dec_chain(hipStream_t st, const ParScan *ps, int nps, uint64_t *state, uint32_t *nblk, const uint16_t *hyp, const uint32_t *scan_pending, uint32_t *need_seq) {
-    if (nps) CSH_LAUNCH(k_dec_chain, dim3((nps + 63) / 64), dim3(64), st, ps, nps, state, nblk, hyp, scan_pending, need_seq);
+void launch_dec_chain(hipStream_t st, const ParScan *ps, int nps, uint64_t *state, uint32_t *nblk, const uint16_t *hyp, const uint32_t *scan_pending, uint32_t *need_seq, uint32_t *stats) {
+    if (nps) CSH_LAUNCH(k_dec_chain, dim3((nps + 63) / 64), dim3(64), st, ps, nps, state, nblk, hyp, scan_pending, need_seq, stats);
 }
 void launch_dc_refine(hipStream_t st, const uint8_t *clean, const ParScan *ps, int nps, uint32_t max_blocks, const ImgDesc *imgs, int16_t *coef, const uint32_t *need_seq) {
     if (nps && max_blocks) CSH_LAUNCH(k_dc_refine, dim3((max_blocks + 255) / 256, nps), dim3(256), st, clean, ps, imgs, coef, need_seq);

@@ -140,47 +140,29 @@ __global__ void __launch_bounds__(256) k_png_colors(const PngImg *imgs, const ui
         }
     }
 }
-// one lane per byte of the indexed row: the index of every pixel by hash look-up (exact palette) or by nearest entry (lossy)
-__global__ void __launch_bounds__(256) k_png_indexed(const PngImg *imgs, const PaletteJob *jobs, const unsigned long long *keys, const uint16_t *slot_index, const uint32_t *palettes,
-                                                     const uint8_t *src, uint8_t *dst) {
-    CSH_SHARED uint32_t pal[256];
+// one lane per byte of the indexed row: the index of every pixel by hash look-up in the exact palette.  A quantiser's job (PaletteJob::nearest == 2) is not
+// served here: it goes to k_png_dither
+__global__ void __launch_bounds__(256) k_png_indexed(const PngImg *imgs, const PaletteJob *jobs, const unsigned long long *keys, const uint16_t *slot_index, const uint8_t *src, uint8_t *dst) {
     const PaletteJob j = jobs[blockIdx.y];
     const PngImg &im = imgs[j.image];   // already the new geometry
     const uint32_t y = blockIdx.x;
-    CSH_PHASE_LOOP(2) {
-        if (phase == 0) { if (j.nearest && threadIdx.x < j.npal) pal[threadIdx.x] = palettes[j.pal_off + threadIdx.x]; continue; }
-        if (y >= im.height || j.nearest == 2u) continue;   // (2: the quantiser's jobs go to k_png_dither)
-        const unsigned long long *tab = keys + uint64_t(j.table) * CSP_PAL_SLOTS;
-        const uint16_t *idx = slot_index + uint64_t(j.table) * CSP_PAL_SLOTS;
-        const uint8_t *s = src + j.src_off + uint64_t(y) * j.old_rowbytes;
-        uint8_t *d = dst + j.dst_off + uint64_t(y) * im.rowbytes;
-        const uint32_t per = 8u / j.depth;
-        for (uint32_t bx = threadIdx.x; bx < im.rowbytes; bx += blockDim.x) {
-            uint32_t v = 0;
-            for (uint32_t k = 0; k < per; k++) {
-                const uint32_t x = bx * per + k;
-                if (x >= im.width) break;
-                const uint32_t key = pixel_key(s + uint64_t(x) * j.old_channels * j.old_bps, j.old_channels, j.old_bps);
-                uint32_t index;
-                if (j.nearest) {   // squared distance over a, r, g, b; ties: the lower index
-                    const int a = int(key >> 24), r = int((key >> 16) & 255u), g = int((key >> 8) & 255u), b = int(key & 255u);
-                    uint32_t bd = ~0u;
-                    index = 0;
-                    for (uint32_t q = 0; q < j.npal; q++) {
-                        const uint32_t pq = pal[q];
-                        const int dr = r - int((pq >> 16) & 255u), dg = g - int((pq >> 8) & 255u), db = b - int(pq & 255u), da = a - int(pq >> 24);
-                        const uint32_t dist = uint32_t(dr * dr + dg * dg + db * db + da * da);
-                        if (dist < bd) { bd = dist; index = q; }
-                    }
-                } else {
-                    uint32_t h = key_slot(key);
-                    while (tab[h] != (unsigned long long)key) h = (h + 1) & (CSP_PAL_SLOTS - 1);   // every pixel's colour is in the table
-                    index = idx[h];
-                }
-                v |= index << (8u - j.depth - k * j.depth);
-            }
-            d[bx] = uint8_t(v);
+    if (y >= im.height || j.nearest == 2u) return;
+    const unsigned long long *tab = keys + uint64_t(j.table) * CSP_PAL_SLOTS;
+    const uint16_t *idx = slot_index + uint64_t(j.table) * CSP_PAL_SLOTS;
+    const uint8_t *s = src + j.src_off + uint64_t(y) * j.old_rowbytes;
+    uint8_t *d = dst + j.dst_off + uint64_t(y) * im.rowbytes;
+    const uint32_t per = 8u / j.depth;
+    for (uint32_t bx = threadIdx.x; bx < im.rowbytes; bx += blockDim.x) {
+        uint32_t v = 0;
+        for (uint32_t k = 0; k < per; k++) {
+            const uint32_t x = bx * per + k;
+            if (x >= im.width) break;
+            const uint32_t key = pixel_key(s + uint64_t(x) * j.old_channels * j.old_bps, j.old_channels, j.old_bps);
+            uint32_t h = key_slot(key);
+            while (tab[h] != (unsigned long long)key) h = (h + 1) & (CSP_PAL_SLOTS - 1);   // every pixel's colour is in the table
+            v |= idx[h] << (8u - j.depth - k * j.depth);
         }
+        d[bx] = uint8_t(v);
     }
 }
 // ---- the lossy row's pixels to palette entries with Floyd-Steinberg error diffusion (oracle: quantize).  One workgroup per picture, a lane per ROW: row r is
@@ -627,8 +609,8 @@ void launch_png_colors(hipStream_t st, const PngImg *imgs, uint32_t total_rows, 
     if (total_rows) CSH_LAUNCH(k_png_colors, dim3(total_rows), dim3(256), st, imgs, row_image, pix, cand, keys, counts, status);
 }
 void launch_png_indexed(hipStream_t st, const PngImg *imgs, const PaletteJob *jobs, int njobs, uint32_t max_height, const unsigned long long *keys, const uint16_t *slot_index,
-                        const uint32_t *palettes, const uint8_t *src, uint8_t *dst) {
-    if (njobs) CSH_LAUNCH_PHASED(k_png_indexed, 2, dim3(max_height, njobs), dim3(256), st, imgs, jobs, keys, slot_index, palettes, src, dst);
+                        const uint8_t *src, uint8_t *dst) {
+    if (njobs) CSH_LAUNCH(k_png_indexed, dim3(max_height, njobs), dim3(256), st, imgs, jobs, keys, slot_index, src, dst);
 }
 // nsteps: the largest (bands x steps per band) of the jobs that dither; lines: two rows of width x 4 int16 per such job (PaletteJob::line_off, in pixels)
 void launch_png_dither(hipStream_t st, const PngImg *imgs, const PaletteJob *jobs, int njobs, int nsteps, const uint32_t *palettes, const uint8_t *src, uint8_t *dst, int16_t *lines) {

@@ -69,8 +69,11 @@ void launch_dec_dense(hipStream_t st, int mode /*0 speculate, 1 relax, 2 write*/
 // launch_dec_seed then lists the first sub-sequence of every group (seed_off: the exclusive scan of DenseArgs::seed_cnt) for a list round that does not walk
 void launch_dec_spec_group(hipStream_t st, int nps, uint32_t max_sub, uint32_t group, uint32_t lanes, const DenseArgs &a);
 void launch_dec_seed(hipStream_t st, const uint64_t *seed_off, int nps, uint32_t max_sub, uint32_t group, uint64_t *list, uint32_t *cnt);
+// counters of the rescue paths, CSH_DEC_NSTATS words behind the images' need_seq words (they are zeroed and read back with them): walk steps of the list rounds' lanes,
+// scans k_dec_chain entered, and those of them it handed to the sequential kernel (csh_timing.n_dec_walked / n_dec_chain_scans / n_dec_chain_failed)
+enum { CSH_DEC_STAT_WALKED = 0, CSH_DEC_STAT_CHAIN_SCANS = 1, CSH_DEC_STAT_CHAIN_FAILED = 2, CSH_DEC_NSTATS = 3 };
 void launch_dec_relax_list(hipStream_t st, const uint8_t *clean, const ParScan *ps, uint32_t total_sub, const void *huffs, int compact, uint64_t *state, uint32_t *nblk,
-                           const uint64_t *list_in, const uint32_t *cnt_in, uint64_t *list_out, uint32_t *cnt_out, size_t nstate, uint32_t *claim, uint32_t epoch, bool walk = true);
+                           const uint64_t *list_in, const uint32_t *cnt_in, uint64_t *list_out, uint32_t *cnt_out, size_t nstate, uint32_t *claim, uint32_t epoch, uint32_t *stats, bool walk = true);
 // progressive inputs: one wave per chain of scans (k_decode_prog.hip); images with need_seq == 4
 // AC refinement chains of progressive inputs (k_decode_refine.hip): history masks, the serial parse (one wave per chain), the parallel apply
 void launch_refine_chains(hipStream_t st, const uint8_t *clean, const ParScan *pss, const ParHuffSet *huffs, const DecScan *scans, const ProgChain *chains,
@@ -83,7 +86,7 @@ void launch_make_slots(hipStream_t st, const ScanWork *works, uint32_t nworks, c
 void launch_decode_prog(hipStream_t st, const uint8_t *clean, const ParScan *pss, const ParHuffSet *huffs, const DecScan *scans, const ProgChain *chains,
                         const int *chain_scans, int nchains, const ImgDesc *imgs, int16_t *coef, uint32_t *need_seq);
 void launch_dec_mark_pending(hipStream_t st, const ParScan *ps, uint32_t total_sub, const uint64_t *list_in, const uint32_t *cnt_in, uint32_t *scan_pending);
-void launch_dec_chain(hipStream_t st, const ParScan *ps, int nps, uint64_t *state, uint32_t *nblk, const uint16_t *hyp, const uint32_t *scan_pending, uint32_t *need_seq);
+void launch_dec_chain(hipStream_t st, const ParScan *ps, int nps, uint64_t *state, uint32_t *nblk, const uint16_t *hyp, const uint32_t *scan_pending, uint32_t *need_seq, uint32_t *stats);
 void launch_dc_refine(hipStream_t st, const uint8_t *clean, const ParScan *ps, int nps, uint32_t max_blocks, const ImgDesc *imgs, int16_t *coef, const uint32_t *need_seq);   // after launch_dc_scatter
 void launch_dc_scatter(hipStream_t st, const ParScan *ps, int nps, uint32_t max_blocks, const ImgDesc *imgs, const uint64_t *dc_off, int16_t *coef,
                        const uint32_t *need_seq, const uint32_t *cut_block);

@@ -255,8 +255,8 @@ static int batch_run(csh_batch *b, csh_timing *t, bool requant_only) {
         csh_set_error("D2H of sizes failed"); return CS_ERR_NO_DEVICE;
     }
     if (t) {
-        std::vector<uint32_t> ns(b->nimg);
-        if (csh_copy_wait(ns.data(), b->dec.d_need_seq.p, b->nimg * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream) != hipSuccess) return CS_ERR_NO_DEVICE;
+        std::vector<uint32_t> ns(size_t(b->nimg) + CSH_DEC_NSTATS);   // the images' words and the decoder's counters behind them
+        if (csh_copy_wait(ns.data(), b->dec.d_need_seq.p, ns.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream) != hipSuccess) return CS_ERR_NO_DEVICE;
         if (getenv("CSH_TRACE") && b->dec.d_relax_cnt.n) {   // sub-sequences re-listed after each relaxation round
             std::vector<uint32_t> rc(b->dec.d_relax_cnt.n);
             if (csh_copy_wait(rc.data(), b->dec.d_relax_cnt.p, rc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream) == hipSuccess) {
@@ -265,6 +265,8 @@ static int batch_run(csh_batch *b, csh_timing *t, bool requant_only) {
                 fprintf(stderr, "\n");
             }
         }
+        t->n_dec_walked = ns[size_t(b->nimg) + CSH_DEC_STAT_WALKED]; t->n_dec_chain_scans = ns[size_t(b->nimg) + CSH_DEC_STAT_CHAIN_SCANS]; t->n_dec_chain_failed = ns[size_t(b->nimg) + CSH_DEC_STAT_CHAIN_FAILED];
+        ns.resize(b->nimg);
         for (const ProgChain &pc : b->dec.chains) if (pc.refine && ns[size_t(pc.image)] == 4) t->n_refine_chains++;
         for (uint32_t v : ns) { if (v == 4) { t->n_prog_decoded++; continue; } if (v) t->n_seq_decoded++; if (v == 2 || v == 3) t->n_par_fallback++; if (v == 3) t->n_par_short++; }
         t->n_images = uint32_t(b->nimg);
@@ -274,7 +276,7 @@ static int batch_run(csh_batch *b, csh_timing *t, bool requant_only) {
         t->n_ac_in_lists = b->enc.last_run_ac_lists;
         t->n_list_runs = b->enc.last_run_list_runs;
         t->n_ref_packed = b->enc.last_run_ref_packed;
-        t->n_dec_group = b->dec.group; t->n_dec_seeds = b->dec.last_run_seeds; t->n_dec_relaxed = b->dec.last_run_relaxed;
+        t->n_dec_group = b->dec.group; t->n_dec_seeds = b->dec.last_run_seeds; t->n_dec_relaxed = b->dec.last_run_relaxed; t->n_dec_rounds = b->dec.last_run_rounds;
         for (const Item &it : b->items) if (it.image < 0) t->n_failed++;
         for (int i = 0; i < b->nimg; i++) { t->out_bytes += b->out.h_img_size[i]; t->pixels += uint64_t(b->imgs[i].width) * b->imgs[i].height; }
         t->in_bytes = b->dec.bits_pool.size();

@@ -35,7 +35,7 @@ struct PaletteJob {
 void launch_png_colors(hipStream_t st, const PngImg *imgs, uint32_t total_rows, const uint32_t *row_image, const uint8_t *pix, const uint32_t *cand, unsigned long long *keys,
                        uint32_t *counts, const uint32_t *status);
 void launch_png_indexed(hipStream_t st, const PngImg *imgs, const PaletteJob *jobs, int njobs, uint32_t max_height, const unsigned long long *keys, const uint16_t *slot_index,
-                        const uint32_t *palettes, const uint8_t *src, uint8_t *dst);
+                        const uint8_t *src, uint8_t *dst);
 enum { CSP_DITHER_ROWS = 512 };   // rows of a picture that advance together in k_png_dither (two waves per SIMD: 256 rows took 12 160 steps for a 1080p picture at the same time per step, 1024 rows 7 936 at twice the time)
 void launch_png_dither(hipStream_t st, const PngImg *imgs, const PaletteJob *jobs, int njobs, int nsteps, const uint32_t *palettes, const uint8_t *src, uint8_t *dst, int16_t *lines);
 

@@ -290,7 +290,7 @@ int relayout_and_repack(csp_batch *b, const std::vector<size_t> &item_of, Reduct
     DevBuf<uint8_t> d_remaps;
     if (d_remaps.upload(R.remaps, st)) return -1;
     launch_png_repack(st, b->d_imgs.p, b->d_jobs.p, int(R.jobs.size()) - 1, R.max_height, b->d_work.p, b->d_work.p, d_remaps.p);
-    launch_png_indexed(st, b->d_imgs.p, b->d_pjobs.p, int(R.pjobs.size()) - 1, R.max_height, b->d_keys.p, b->d_slot_index.p, b->d_qpal.p, b->d_work.p, b->d_work.p);
+    launch_png_indexed(st, b->d_imgs.p, b->d_pjobs.p, int(R.pjobs.size()) - 1, R.max_height, b->d_keys.p, b->d_slot_index.p, b->d_work.p, b->d_work.p);
     DevBuf<int16_t> d_lines;   // the error rows the bands of k_png_dither hand down (freed behind the synchronisation below)
     if (R.dither_steps) {
         if (R.dither_steps > 0x3FFFFFFFull || d_lines.alloc(size_t(R.dither_pixels) * 4 + 4)) { csh_set_error("PNG dither buffers failed"); return -1; }

@@ -154,6 +154,10 @@ typedef struct {
                                      parallel-decoded scans and restart segments of ceil(live sub-sequences / n_dec_group); 1: what the dense relaxation pass listed */
     uint32_t n_dec_relaxed;       /* sub-sequence evaluations the relaxation asked for in this run: the sum of the list's length in front of every round, the seam round included
                                      (n_dec_group = 1: plus the live sub-sequences, which the dense relaxation pass evaluated).  Sub-sequences a lane walked on into are not counted */
+    uint32_t n_dec_rounds;        /* list rounds this run launched behind the first relaxation pass (the seam round is not one of them).  At most CSH_TEST_DEC_ROUNDS where the tests set it */
+    uint32_t n_dec_walked;        /* sub-sequences a lane of a list round walked on into (up to seven a lane and round), instead of listing them for the next round */
+    uint32_t n_dec_chain_scans;   /* scans and restart segments still listed behind the last round, whose block-in-MCU labels the label chain (k_dec_chain) set out to settle */
+    uint32_t n_dec_chain_failed;  /* of those, the ones it could not settle: their images went to the sequential kernel and are counted in n_par_fallback */
 } csh_timing;
 
 int csh_device_count(void);

@@ -705,6 +705,143 @@ def unit_wavereader(lib, wpb):
     same(f"{name}: insufficient(), true exactly once more bits were taken than the buffer holds", over, wo)
 
 
+# ---------------------------------------------------------------------------------------------------- k_decode_par.hip: the label chain
+# k_dec_mark_pending + k_dec_chain on made-up arrays.  The model is the comment above the two kernels, nothing else: a scan named by the list is pending; a
+# pending scan the parallel decoder decodes is walked from label 0 through the (exit label, block count) maps of its live sub-sequences -- every visited
+# sub-sequence gets its entry label and, unless the walk ends there, its count -- and the first unusable hypothesis (0xFFFF), or an AC first scan, which has
+# no label to settle, gives the image to the sequential kernel (need_seq = 2).
+SUBSEQ = 128
+PS_SEQ, PS_UNSTUFF, PS_DC_FIRST, PS_AC_FIRST, PS_DC_REFINE = range(5)   # types.h CSH_PS_*
+DEC_NSTATS = 3                                                         # kernels.h: walked, chain scans, chain failed -- behind the images' need_seq words
+
+
+def chain_model(scans, state, nblk, hyp, listed, need_seq, nimg):
+    state, nblk, need_seq = state.copy(), nblk.copy(), need_seq.copy()
+    pending = np.zeros(len(scans), np.uint32)
+    for e in listed: pending[int(e) >> 32] = 1
+    for i, (kind, image, nb_mcu, bits_len, clean_len, sub_base) in enumerate(scans):
+        if not pending[i] or kind not in (PS_SEQ, PS_DC_FIRST, PS_AC_FIRST): continue
+        need_seq[nimg + 1] += 1
+        m, failed = 0, kind == PS_AC_FIRST
+        for t in range(0 if failed else min((bits_len + SUBSEQ - 1) // SUBSEQ, (clean_len + SUBSEQ - 1) // SUBSEQ)):
+            state[sub_base + i + t] = (int(state[sub_base + i + t]) & ~0xFF00) | (m << 8)
+            h = int(hyp[sub_base + t, m])
+            if h == 0xFFFF: failed = True; break
+            nblk[sub_base + t], m = h & 4095, h >> 12
+        if failed: need_seq[image] = 2; need_seq[nimg + 2] += 1
+    return state, nblk, pending, need_seq
+
+
+class ChainCall:
+    """the arrays of one call: scans are added with their hypotheses; everything the kernels do not write starts as junk"""
+    def __init__(self, seed, nimg):
+        self.rng, self.nimg, self.scans, self.rows, self.listed = np.random.default_rng(seed), nimg, [], [], []
+
+    def path(self, rows):
+        m, out = 0, []
+        for r in rows:
+            out.append(m); m = int(r[m]) >> 12
+        return out
+
+    def add(self, kind=PS_SEQ, image=0, nb_mcu=3, nsub=6, clean_len=None, pending=True, maps=None, fail_at=None, count=None, tail=0):
+        """nsub sub-sequences; maps[t][m] = exit label (default: random below nb_mcu); fail_at: the live sub-sequence whose hypothesis ON the walk's path is
+        unusable; count: one block count for all (default random); tail: bytes of bits_len behind a whole number of sub-sequences"""
+        rng = self.rng
+        bits_len = nsub * SUBSEQ - (SUBSEQ - tail if tail else 0)
+        rows = np.zeros((nsub, 10), np.uint16)
+        for t in range(nsub):
+            for m in range(10):
+                lab = maps[t][m] if maps is not None else int(rng.integers(0, nb_mcu))
+                rows[t, m] = (lab << 12) | (count if count is not None else int(rng.integers(0, 4096)))
+        walk = self.path(rows)
+        for t in range(nsub):   # unusable hypotheses OFF the path change nothing
+            for m in range(10):
+                if m != walk[t] and rng.integers(0, 4) == 0: rows[t, m] = 0xFFFF
+        if fail_at is not None: rows[fail_at, walk[fail_at]] = 0xFFFF
+        sub_base = sum(len(r) for r in self.rows)
+        self.scans.append((kind, image, nb_mcu, bits_len, bits_len if clean_len is None else clean_len, sub_base))
+        self.rows.append(rows)
+        if pending:   # at one or several of its sub-sequences (a list is never longer than there are sub-sequences)
+            for t in rng.permutation(nsub)[:int(rng.integers(1, 4))]: self.listed.append((len(self.scans) - 1) << 32 | int(t))
+
+    def check(self, lib, what):
+        rng, nps, nimg = self.rng, len(self.scans), self.nimg
+        hyp = np.concatenate(self.rows)
+        total = len(hyp)
+        state = (rng.integers(0, 1 << 32, total + nps).astype(np.uint64) << np.uint64(16)) | rng.integers(0, 1 << 16, total + nps).astype(np.uint64)   # pos << 16 | junk label << 8 | k
+        nblk = rng.integers(0, 1 << 32, total).astype(np.uint32)
+        need = np.concatenate([rng.choice(np.array([0, 0, 1, 4], np.uint32), nimg), rng.integers(0, 1000, DEC_NSTATS).astype(np.uint32)])
+        listed = np.array(self.listed, np.uint64)[rng.permutation(len(self.listed))] if self.listed else np.zeros(0, np.uint64)
+        scans = np.array(self.scans, np.int32)
+        w_state, w_nblk, w_pending, w_need = chain_model(self.scans, state, nblk, hyp, listed, need, nimg)
+        pending = np.full(nps, 0x55555555, np.uint32)
+        lib.run("csdu_dec_chain", nps, scans, nimg, total, state, nblk, hyp, np.concatenate([listed, np.zeros(1, np.uint64)]), len(listed), pending, need)
+        same(f"k_dec_mark_pending ({what}): the scans the list names", pending, w_pending)
+        same(f"k_dec_chain ({what}): need_seq (2: to the sequential kernel) and the counters behind it", need, w_need)
+        same(f"k_dec_chain ({what}): the entry labels in the states", state, w_state)
+        same(f"k_dec_chain ({what}): the block counts", nblk, w_nblk)
+        return w_need, w_pending
+
+
+def unit_dec_chain(lib):
+    """the label chain of the parallel JPEG decoder against chain_model"""
+    # one to five scans, every mix of pending and not
+    for n in range(1, 6):
+        for mask in range(1 << n):
+            c = ChainCall(1000 + 32 * n + mask, nimg=n)
+            for i in range(n): c.add(image=i, nb_mcu=(1, 3, 4, 6, 10)[i], nsub=1 + (3 * i + mask) % 7, pending=bool(mask >> i & 1), fail_at=0 if (mask >> i & 1) and (i + mask) % 3 == 0 else None)
+            c.check(lib, f"{n} scans, pending mask {mask:0{n}b}")
+    # the kinds: an AC first scan has no label to settle; what the parallel decoder does not decode is left alone though it is listed
+    c = ChainCall(2, nimg=5)
+    for i, kind in enumerate((PS_AC_FIRST, PS_UNSTUFF, PS_DC_REFINE, PS_DC_FIRST, PS_SEQ)): c.add(kind=kind, image=i, nb_mcu=1 if kind != PS_SEQ else 6, nsub=4)
+    w_need, _ = c.check(lib, "one scan of every kind, all listed")
+    assert [int(v == 2) for v in w_need[:5]] == [1, 0, 0, 0, 0]   # (the battery means what it says)
+    # an unusable hypothesis at the first, a middle and the last live sub-sequence, and just behind the live range
+    c = ChainCall(3, nimg=8)
+    c.add(image=0, nsub=7, fail_at=0); c.add(image=1, nsub=7, fail_at=3); c.add(image=2, nsub=7, fail_at=6)
+    c.add(image=3, nsub=7, clean_len=4 * SUBSEQ + 1, fail_at=4)                   # five live sub-sequences: the last of them
+    c.add(image=4, nsub=7, clean_len=4 * SUBSEQ + 1, fail_at=5)                   # ... the first that is not live: nothing fails
+    c.add(image=5, nsub=7, clean_len=4 * SUBSEQ, fail_at=4)                       # the data ends exactly on a cut: four live
+    c.add(image=6, nsub=7, clean_len=4 * SUBSEQ, fail_at=3)
+    c.add(image=7, nsub=7, clean_len=7 * SUBSEQ - 100, tail=28, fail_at=6)        # clean_len == bits_len, a partial last sub-sequence
+    w_need, _ = c.check(lib, "0xFFFF first / middle / last, live range ended by clean_len")
+    assert [int(v) == 2 for v in w_need[:8]] == [True, True, True, True, False, False, True, True]
+    # the data ends before nsub, at it, and not at all (clean_len = 0: no live sub-sequence, nothing written, nothing failed)
+    c = ChainCall(4, nimg=3)
+    c.add(image=0, nsub=9, clean_len=2 * SUBSEQ + 64); c.add(image=1, nsub=9, clean_len=9 * SUBSEQ); c.add(image=2, nsub=9, clean_len=0, fail_at=0)
+    w_need, _ = c.check(lib, "clean_len before nsub, at nsub, zero")
+    assert not (w_need[:3] == 2).any()
+    # label maps that cycle through all ten labels, with steps of 1, 3, 7 and 9; a count of 4095 and of 0 everywhere
+    c = ChainCall(5, nimg=6)
+    for i, step in enumerate((1, 3, 7, 9)): c.add(image=i, nb_mcu=10, nsub=23, maps=[[(m + step) % 10 for m in range(10)]] * 23)
+    c.add(image=4, nb_mcu=10, nsub=12, count=4095, maps=[[(m + 1) % 10 for m in range(10)]] * 12)
+    c.add(image=5, nb_mcu=4, nsub=5, count=0)
+    c.check(lib, "cycles through ten labels, counts 4095 and 0")
+    # two scans (restart segments) of one image of which one fails; beside an image whose scans all settle and one that is not pending
+    c = ChainCall(6, nimg=3)
+    c.add(image=0, nsub=5); c.add(image=0, nsub=5, fail_at=2); c.add(image=0, nsub=3, pending=False)
+    c.add(image=1, nsub=4); c.add(image=1, nsub=4)
+    c.add(image=2, nsub=4, pending=False, fail_at=0)
+    w_need, w_pending = c.check(lib, "two scans of one image, one fails")
+    assert w_need[0] == 2 and w_need[1] != 2 and w_need[2] != 2 and w_pending.tolist() == [1, 1, 0, 1, 1, 0]
+    # more scans than a workgroup of k_dec_chain has lanes, everything at random
+    c = ChainCall(7, nimg=40)
+    r = np.random.default_rng(70)
+    for i in range(150):
+        nsub = int(r.integers(1, 14))
+        c.add(kind=int(r.choice([PS_SEQ] * 6 + [PS_DC_FIRST, PS_AC_FIRST, PS_UNSTUFF, PS_DC_REFINE])), image=int(r.integers(0, 40)), nb_mcu=int(r.choice([1, 3, 4, 6, 10])), nsub=nsub,
+              clean_len=int(r.integers(0, nsub * SUBSEQ + 1)) if r.integers(0, 2) else None, pending=bool(r.integers(0, 3)), fail_at=int(r.integers(0, nsub)) if r.integers(0, 4) == 0 else None)
+    c.check(lib, "150 scans at random")
+    # refused before anything is launched: what would index outside the arrays
+    z64, z32, z16 = np.zeros(8, np.uint64), np.zeros(8, np.uint32), np.zeros(40, np.uint16)
+    ok = np.array([[PS_SEQ, 0, 3, 4 * SUBSEQ, 4 * SUBSEQ, 0]], np.int32)
+    assert lib.call("csdu_dec_chain", 1, ok, 1, 4, z64, z32, z16, z64, 1, z32, z32) == 0
+    for bad in ([PS_SEQ, 1, 3, 4 * SUBSEQ, 4 * SUBSEQ, 0], [PS_SEQ, 0, 3, 5 * SUBSEQ, 4 * SUBSEQ, 0], [PS_SEQ, 0, 3, 4 * SUBSEQ, 4 * SUBSEQ, 1], [5, 0, 3, 4 * SUBSEQ, 4 * SUBSEQ, 0], [PS_SEQ, 0, 11, SUBSEQ, SUBSEQ, 0]):
+        assert lib.call("csdu_dec_chain", 1, np.array([bad], np.int32), 1, 4, z64, z32, z16, z64, 1, z32, z32) == -1, bad
+    assert lib.call("csdu_dec_chain", 1, ok, 1, 4, z64, z32, np.full(40, 0xA000, np.uint16), z64, 1, z32, z32) == -1          # an exit label of ten
+    assert lib.call("csdu_dec_chain", 1, ok, 1, 4, z64, z32, z16, np.full(8, 1 << 32, np.uint64), 1, z32, z32) == -1          # the list names a scan that is not there
+
+
 # ---------------------------------------------------------------------------------------------------- png_lz.h
 def unit_lz(lib):
     """load32u / load64u at every misalignment, and align_bytes.  align_bytes' contract: shift <= 3 -- the device instruction takes the low two bits of it, the
@@ -939,6 +1076,7 @@ def _units():
     u["code_entries_refuse"] = unit_code_entries_refuse
     u["load_unaligned_align_bytes"] = unit_lz
     u["dither_distance"] = unit_dither_dist
+    u["dec_chain"] = unit_dec_chain
     return u
 
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import _gif_model as M
+import _lzw_probe as L
 import _gif_write as W
 from _util import ROOT, emul_api, package
 
@@ -152,6 +153,12 @@ def output_cases():
     # disposal 3: the block of frame 1 is taken back before frame 2 paints its own
     fr = moving_block(15, 3, 37)
     cases["disposal 3"] = naive([fr[0], np.where(fr[1] != fr[0], fr[1], 15), np.where(fr[2] != fr[1], fr[2], 15)], g16, transparent=15, disposals=[1, 3, 1])
+    # the coder's dictionary look-up in its second step of 64 slots (tests/_lzw_probe.py; the replay proves each string does it): one row of 256 distinct colours, so
+    # the coder is fed the string itself at code size 8.  (Nearly all of it codes as literals: the input is written in sub-blocks of one byte, so that the output is the smaller file.)
+    for name, home, wraps in (("coder's second probe step", L.FIRST, False), ("coder's second probe step across the table's end", L.WRAPPING, True)):
+        L.check(L.probe_string(home), 4096, wraps)
+        idx = np.frombuffer(L.probe_string(home), np.uint8).astype(np.int64).reshape(1, -1)
+        cases[name] = W.gif(idx.shape[1], 1, [W.frame(idx, disposal=1, delay=5, clears=254, sub=1)], gct=g256, loop=0)
     return cases
 
 

@@ -139,6 +139,36 @@ def test_emul_two_dc_refinement_passes(api):
     assert api.batch_compress(srcs, params()) == [oracle_lossy(s) for s in srcs]
 
 
+def dc_scans_by_component_file(seed, w, h, ss, texture=30):
+    """a regular progression whose DC scans -- the first one, at Al = 1, and its refinement -- come one per component: a non-interleaved scan walks the
+    component's own block grid (real_bw x real_bh, without the blocks that pad it to whole MCUs), not the MCU grid"""
+    from oracle import oracle as O
+    ci = O.decode(synth_jpeg(seed, w, h, subsampling=ss, texture=texture))
+    script = [((0,), 0, 0, 0, 1), ((1,), 0, 0, 0, 1), ((2,), 0, 0, 0, 1), ((0,), 1, 63, 0, 1), ((1,), 1, 63, 0, 0), ((2,), 1, 63, 0, 0),
+              ((2,), 0, 0, 1, 0), ((0,), 0, 0, 1, 0), ((0,), 1, 63, 1, 0), ((1,), 0, 0, 1, 0)]
+    return ci.encode(O.params(progressive=1, marker_style=0), script=script)
+
+
+def test_emul_dc_scans_of_one_component(api, monkeypatch):
+    """k_decode_prog.hip scan_dc_first / scan_dc_refine for a scan of one component.  They run where the whole file stays on the ordered chains
+    (batch_plan.cpp progressive_plan: par_first false -- CSH_PROG_PAR=0, or an irregular progression); by default the same scans go to the parallel decoder
+    and k_dc_refine.  Pictures that are no whole number of MCUs: 4:2:0 at 203 x 155 and at 200 x 150 (luma: 25 x 19 blocks of the 26 x 20 the MCUs span),
+    4:2:2 at 50 x 34 (7 x 5 of 8 x 5)"""
+    srcs = [dc_scans_by_component_file(5, 203, 155, 2), dc_scans_by_component_file(6, 50, 34, 1), dc_scans_by_component_file(7, 200, 150, 2, 50)]
+    lossless, lossy = [oracle_lossless(s) for s in srcs], [oracle_lossy(s) for s in srcs]
+    for mode in ("0", None, "1"):
+        if mode is None: monkeypatch.delenv("CSH_PROG_PAR", raising=False)
+        else: monkeypatch.setenv("CSH_PROG_PAR", mode)
+        for want, p in ((lossless, params(jpeg_optimize=True)), (lossy, params())):
+            bt = api.batch(srcs, p)
+            t = bt.run()
+            assert t.n_prog_decoded == len(srcs) and t.n_seq_decoded == 0 and t.n_par_fallback == 0, mode   # the route's witness
+            if mode == "0": assert t.n_refine_chains == 0 and t.n_dec_seeds == 0   # every scan on the chains: nothing for the parallel decoder to list
+            for i, (w_, out) in enumerate(zip(want, bt.fetch())):
+                assert out == w_, (mode, i)
+    monkeypatch.delenv("CSH_PROG_PAR", raising=False)
+
+
 def test_emul_irregular_progressions_decode_in_file_order(api):
     """a damaged scan header can make two first scans cover one band, or a refinement scan come before the band's first scan: libjpeg warns and decodes in file
     order (the later scan wins).  The parallel kinds of the progressive decoder run side by side, so such a file must stay on the ordered chains"""

@@ -116,6 +116,10 @@ def test_two_dc_refinement_passes(api):
         E.test_emul_two_dc_refinement_passes(api)
 
 
+def test_dc_scans_of_one_component(api, monkeypatch):
+    E.test_emul_dc_scans_of_one_component(api, monkeypatch)
+
+
 def test_non_interleaved_sequential_scans(api):
     E.test_emul_non_interleaved_sequential_scans(api)
 

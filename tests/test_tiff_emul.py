@@ -12,6 +12,7 @@ import zlib
 import numpy as np
 import pytest
 
+import _lzw_probe as L
 import _tiff_model as M
 import _tiff_write as W
 from _util import ROOT, emul_api, package
@@ -88,6 +89,10 @@ def decoder_cases():
     c.append(("lzw no EOI, surplus bytes that read as codes beyond the table", W.tiff([W.page(noise(CW * CH, 24, 16), CW, CH, compression=W.LZW, rows_per_strip=9, lzw=dict(eoi=False), surplus=b"\xff" * 9)])))
     c.append(("lzw surplus bytes", W.tiff([W.page(noise(CW * CH, 11, 16), CW, CH, compression=W.LZW, rows_per_strip=16, surplus=b"\x55" * 7)])))
     c += switch_strips()
+    # the encoder's dictionary look-up in its second step of 64 slots (tests/_lzw_probe.py; the replay proves each string does it): one row, one segment at any CSH_TIFF_STRIP
+    for name, home, wraps in (("lzw encoder's second probe step", L.FIRST, False), ("lzw encoder's second probe step across the table's end", L.WRAPPING, True)):
+        L.check(L.probe_string(home), 4094, wraps)
+        c.append((name, W.tiff([W.page(L.probe_string(home), len(L.probe_string(home)), 1, compression=W.LZW)])))
     c.append(("1 x 1", W.tiff([W.page(b"\x7f", 1, 1, compression=W.LZW)])))
     c.append(("one-row strips", W.tiff([W.page(noise(CW * 5, 12), CW, 5, compression=W.LZW, rows_per_strip=1)], big_endian=True)))
     c.append(("a last strip of one row", W.tiff([W.page(noise(CW * 41, 13), CW, 41, compression=W.PACKBITS, rows_per_strip=8)])))
@@ -153,7 +158,7 @@ def test_emul_decoder_tap_equals_the_model(api):
 def output_cases():
     """[(name, file, what Predictor 2 must do on the LZW route: True wins, False loses, None not asked)]"""
     pick = ("lzw noise spp 3", "lzw full table, Clear by the text", "one-row strips", "a last strip of one row", "packbits runs of 2 3 128 129 300", "deflate level 9", "uncompressed", "predictor 16-bit MM",
-            "tiles 16 x 16 on 50 x 41, predictor 2", "two pages, two compressions", "1-bit rows", "palette", "1 x 1")
+            "tiles 16 x 16 on 50 x 41, predictor 2", "two pages, two compressions", "1-bit rows", "palette", "1 x 1", "lzw encoder's second probe step", "lzw encoder's second probe step across the table's end")
     c = [(n, b, None) for n, b in decoder_cases() if n in pick]
     assert len(c) == len(pick)
     c.append(("smooth gradient", W.tiff([W.page(gradient(CW, CH, 3), CW, CH, spp=3, photometric=2)]), True))
