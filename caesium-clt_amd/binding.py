@@ -26,12 +26,12 @@ class CByteArray(C.Structure):
 
 class Timing(C.Structure):
     _fields_ = [("total_ms", C.c_float), ("phase_ms", C.c_float * NPHASES), ("kernel_ms", C.c_float * NKERNELS), ("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64),
-                ("pixels", C.c_uint64), ("coef_bytes", C.c_uint64), ("n_images", C.c_uint32), ("n_failed", C.c_uint32), ("n_seq_decoded", C.c_uint32), ("n_par_fallback", C.c_uint32), ("n_par_short", C.c_uint32), ("n_prog_decoded", C.c_uint32), ("n_refine_chains", C.c_uint32), ("n_search_extra", C.c_uint32), ("n_fused_lists", C.c_uint32), ("n_list_refine", C.c_uint32), ("n_ac_in_lists", C.c_uint32), ("n_list_runs", C.c_uint32), ("n_ref_packed", C.c_uint32), ("n_dec_group", C.c_uint32), ("n_dec_seeds", C.c_uint32), ("n_dec_relaxed", C.c_uint32), ("n_dec_rounds", C.c_uint32), ("n_dec_walked", C.c_uint32), ("n_dec_chain_scans", C.c_uint32), ("n_dec_chain_failed", C.c_uint32)]
+                ("pixels", C.c_uint64), ("coef_bytes", C.c_uint64), ("n_images", C.c_uint32), ("n_failed", C.c_uint32), ("n_seq_decoded", C.c_uint32), ("n_par_fallback", C.c_uint32), ("n_par_short", C.c_uint32), ("n_prog_decoded", C.c_uint32), ("n_refine_chains", C.c_uint32), ("n_search_extra", C.c_uint32), ("n_fused_lists", C.c_uint32), ("n_list_refine", C.c_uint32), ("n_ac_in_lists", C.c_uint32), ("n_list_runs", C.c_uint32), ("n_ref_packed", C.c_uint32), ("n_dec_group", C.c_uint32), ("n_dec_seeds", C.c_uint32), ("n_dec_relaxed", C.c_uint32), ("n_dec_rounds", C.c_uint32), ("n_dec_walked", C.c_uint32), ("n_dec_chain_scans", C.c_uint32), ("n_dec_chain_failed", C.c_uint32), ("n_pool_retries", C.c_uint32)]
 
 
 class PngTiming(C.Structure):
     _fields_ = [("total_ms", C.c_float), ("kernel_ms", C.c_float * 16), ("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("pixels", C.c_uint64),
-                ("raw_bytes", C.c_uint64), ("n_images", C.c_uint32), ("n_failed", C.c_uint32), ("n_trials", C.c_uint32)]
+                ("raw_bytes", C.c_uint64), ("n_images", C.c_uint32), ("n_failed", C.c_uint32), ("n_trials", C.c_uint32), ("n_pool_retries", C.c_uint32)]
 
 
 class GifTiming(C.Structure):
@@ -55,7 +55,7 @@ def library_path():
 
 
 EXPORTS = ["cs_default_parameters", "cs_compress_in_memory", "cs_compress_to_size_in_memory", "cs_convert_in_memory",
-           "cs_batch_compress", "cs_batch_extent", "cs_free_bytes", "cs_free_result", "csh_device_count", "csh_last_error", "csh_kernel_name", "csh_kernel_name_webp", "csh_release_cached_memory", "csh_warmup", "csh_batch_create",
+           "cs_batch_compress", "cs_batch_extent", "cs_free_bytes", "cs_free_result", "csh_device_count", "csh_last_error", "csh_last_pool_retries", "csh_kernel_name", "csh_kernel_name_webp", "csh_release_cached_memory", "csh_warmup", "csh_batch_create",
            "csh_batch_run", "csh_batch_fetch", "csh_batch_destroy", "csh_batch_retain_dct", "csh_batch_set_quality", "csh_batch_rerun_encode", "cs_batch_compress_to_size", "csh_batch_geometry", "csh_batch_read_coefs",
            "csp_kernel_name", "csp_batch_create", "csp_batch_create_webp", "csp_batch_create_pixels", "csh_batch_create_pixels", "csh_batch_pixels", "csh_batch_create_from_pixels", "csp_png_to_jpeg", "csp_png_to_lossless_webp", "csp_batch_run", "csp_batch_fetch", "csp_batch_destroy", "csp_batch_geometry", "csp_batch_read_rows", "csp_batch_read_stream",
            "csp_batch_trials", "csp_batch_read_scores", "csp_batch_chunk_bits", "csh_batch_create_webp", "cs_batch_convert",
@@ -85,6 +85,8 @@ def _declare(L):
     L.cs_free_result.argtypes = [P(CCSResult)]
     L.cs_free_result.restype = None
     L.csh_last_error.restype = C.c_char_p
+    L.csh_last_pool_retries.argtypes = []
+    L.csh_last_pool_retries.restype = C.c_uint32
     L.csh_kernel_name.argtypes = [C.c_int]
     L.csh_kernel_name.restype = C.c_char_p
     L.csh_kernel_name_webp.argtypes = [C.c_int]
@@ -253,7 +255,7 @@ class Batch:
 class PngBatch:
     """csp_batch: a group of PNG files resident in HBM (the lossless PNG row)."""
 
-    def __init__(self, api, blobs, params, device=0):
+    def __init__(self, api, blobs, params, device=0, webp=False):
         self.api = api
         L = api.L
         self.n = len(blobs)
@@ -263,7 +265,7 @@ class PngBatch:
             self._in[i].data = C.cast(buf, C.POINTER(C.c_uint8))
             self._in[i].length = len(blobs[i])
         self.h = C.c_void_p()
-        rc = L.csp_batch_create(self._in, self.n, C.byref(params), device, C.byref(self.h))
+        rc = (L.csp_batch_create_webp if webp else L.csp_batch_create)(self._in, self.n, C.byref(params), device, C.byref(self.h))
         if rc:
             raise CaesiumError(rc, L.csh_last_error().decode())
 
@@ -690,6 +692,14 @@ class CaesiumHip:
 
     def png_batch(self, blobs, params, device=0):
         return PngBatch(self, blobs, params, device)
+
+    def png_webp_batch(self, blobs, params, device=0):
+        """PNG in, lossy WebP out (csp_batch_create_webp): the files without their alpha plane -- cs_batch_convert attaches that"""
+        return PngBatch(self, blobs, params, device, webp=True)
+
+    def last_pool_retries(self):
+        """csh_last_pool_retries: extra runs with larger pools since the last call of this, on this thread (read and reset)"""
+        return self.L.csh_last_pool_retries()
 
     def png_kernel_names(self):
         return [self.L.csp_kernel_name(i).decode() for i in range(16)]

@@ -229,7 +229,7 @@ struct TrellisPlan {
 
 // the VP8 encoder behind the resize branch (k_webp.hip, k_vp8enc.hip)
 struct WebpTail {
-    uint32_t webp_mb_bytes = 768;  // output bytes reserved per macroblock (grows on overflow)
+    uint32_t webp_mb_bytes = 768;  // output bytes reserved per macroblock (grows on overflow; CSH_TEST_POOL_SHIFT divides this first value: layout_token_pool)
     std::vector<csw::WebpImg> wimgs;
     uint64_t wwork_bytes = 0, wlevels = 0;
     uint32_t wmax_luma = 0, wmax_mbh = 0;
@@ -268,7 +268,7 @@ struct csh_batch {
     bool progressive = true;
     bool retain_dct = false;       // size targeting: keep the unquantised DCT so that another quality only re-quantises
     bool have_dct = false;
-    int q_base = 0;                // quants[q_base + q] = output table for quality q (1..100)
+    int q_base = 0;               // quants[q_base + q] = output table for quality q (1..100)
 
     // what every phase reads: the images, the quantisation tables, the coefficient tiles ([all decoded tiles][all re-quantised tiles])
     std::vector<csh::ImgDesc> imgs;

@@ -217,7 +217,8 @@ void layout_token_pool(csh_batch *b) {
     b->enc.regions.resize(b->enc.region_est.size());
     // CSH_TEST_POOL_SHIFT=n (tests): every estimate divided by 2^n, so that the first runs overflow and the batch goes through its retries with larger pools
     // (read once per batch object, at its first layout: the retries of a run keep what the run started with -- ADVICE r05; an unsupported test hook)
-    if (b->test_pool_shift < 0) b->test_pool_shift = getenv("CSH_TEST_POOL_SHIFT") ? std::min(16, std::max(0, atoi(getenv("CSH_TEST_POOL_SHIFT")))) : 0;
+    // The same read divides the WebP tail's first reservation per macroblock (batch.hpp WebpTail): 768 -> 48 with shift 4, -> 0 with shift 16, which no retry makes larger
+    if (b->test_pool_shift < 0) { b->test_pool_shift = csh_test_pool_shift(); b->wp.webp_mb_bytes >>= b->test_pool_shift; }
     const int shift = b->test_pool_shift;
     uint64_t at = 0;
     for (size_t i = 0; i < b->enc.regions.size(); i++) {

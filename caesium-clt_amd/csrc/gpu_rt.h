@@ -158,6 +158,8 @@ using std::min;
     } while (0)
 
 void csh_set_error(const char *fmt, ...);
+int csh_test_pool_shift();                 // CSH_TEST_POOL_SHIFT as it is now, 0 .. 16 (tests; a batch object reads it once and keeps it: batch_plan.cpp layout_token_pool)
+void csh_count_pool_retries(uint32_t n);   // a batch run of this thread repeated itself n times with larger pools (csh_last_pool_retries)
 
 // A copy the host waits for, ordered on the batch's OWN stream.  A plain hipMemcpy goes through the legacy default stream: it waits for every
 // kernel of every other batch of the process (the second worker's, another file type's), and holds their next launches up until it is done.

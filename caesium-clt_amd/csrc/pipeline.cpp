@@ -21,6 +21,12 @@ void csh_set_error(const char *fmt, ...) {
     va_end(ap);
 }
 extern "C" const char *csh_last_error(void) { return g_err; }
+// the extra runs with larger pools that the batch runs of this thread have made since it was last asked (read and reset): what a one-call entry, which hands
+// out no csh_timing, leaves for a caller that wants to know whether its files went through a retry
+static thread_local uint32_t g_pool_retries = 0;
+void csh_count_pool_retries(uint32_t n) { g_pool_retries += n; }
+extern "C" uint32_t csh_last_pool_retries(void) { const uint32_t n = g_pool_retries; g_pool_retries = 0; return n; }
+int csh_test_pool_shift() { const char *e = getenv("CSH_TEST_POOL_SHIFT"); return e ? std::min(16, std::max(0, atoi(e))) : 0; }
 
 #ifdef CSH_EMUL
 thread_local dim3 threadIdx, blockIdx, blockDim, gridDim;
@@ -230,6 +236,7 @@ static int batch_run(csh_batch *b, csh_timing *t, bool requant_only) {
     if (t) memset(t, 0, sizeof *t);
     if (!b->nimg) { b->out.ran = true; return 0; }
     if (hipSetDevice(b->device) != hipSuccess) { csh_set_error("hipSetDevice failed"); return CS_ERR_NO_DEVICE; }
+    uint32_t retries = 0;
     for (int attempt = 0; attempt < 4; attempt++) {
         if (run_once(b, t, requant_only)) return CS_ERR_NO_DEVICE;
         uint32_t ovf[4] = {0, 0, 0, 0};
@@ -243,8 +250,17 @@ static int batch_run(csh_batch *b, csh_timing *t, bool requant_only) {
             if (b->enc.d_regions.upload(b->enc.regions, b->stream) || b->enc.d_nzlists.upload(b->enc.nzlists, b->stream) || hipStreamSynchronize(b->stream) != hipSuccess) return CS_ERR_NO_DEVICE;
         }
         for (uint32_t s : b->out.h_status) if (s == CS_ERR_POOL_OVERFLOW) pool = true;
+        retries = uint32_t(attempt);
+        if (pool && getenv("CSH_TRACE")) {
+            size_t nfull = 0;
+            for (uint32_t s : b->out.h_status) nfull += s == CS_ERR_POOL_OVERFLOW;
+            fprintf(stderr, "[csh] attempt %d overflowed: raw / output pool %u, token / list pools %u, files without room %zu\n", attempt, ovf[0], ovf[1], nfull);
+        }
         if (!pool) break;
-        if (attempt == 3) { csh_set_error("device pools overflowed after 3 retries"); return CS_ERR_POOL_OVERFLOW; }
+        // A WebP file has a region of its own: the files that fit are whole after any attempt, so the ones that still do not fit fail alone (their status word says
+        // CS_ERR_POOL_OVERFLOW).  The JPEG coder's pools are shared by the batch: there the call fails and the route tries smaller groups
+        if (attempt == 3 && b->webp && !ovf[0] && !ovf[1]) break;
+        if (attempt == 3) { csh_count_pool_retries(retries); if (t) t->n_pool_retries = retries; csh_set_error("device pools overflowed after 3 retries"); return CS_ERR_POOL_OVERFLOW; }
         b->out.raw_bytes_cap *= 4; b->out.out_cap = b->out.raw_bytes_cap;  // rare: output larger than 2x the input
         b->wp.webp_mb_bytes *= 4;
     }
@@ -283,7 +299,9 @@ static int batch_run(csh_batch *b, csh_timing *t, bool requant_only) {
         uint64_t in_tiles = 0;
         for (const ImgDesc &im : b->imgs) for (int c = 0; c < im.ncomp_in; c++) in_tiles += im.in[c].ntiles;
         t->coef_bytes = in_tiles * CSH_TILE_I16 * 2;
+        t->n_pool_retries = retries;
     }
+    csh_count_pool_retries(retries);
     b->out.ran = true;
     if (!requant_only) b->have_dct = (b->retain_dct || b->tr.trellis) && !b->lossless;
     return 0;
@@ -331,7 +349,7 @@ extern "C" int csh_batch_fetch(csh_batch *b, CByteArray *outputs, CCSResult *res
             outputs[n].data = nullptr; outputs[n].length = 0;
             int code = it.code;
             std::string msg = it.msg;
-            if (!code && it.image >= 0 && b->out.h_status[it.image]) { code = int(b->out.h_status[it.image]); msg = "device reported a malformed stream"; }
+            if (!code && it.image >= 0 && b->out.h_status[it.image]) { code = int(b->out.h_status[it.image]); msg = code == CS_ERR_POOL_OVERFLOW ? "device pools overflowed after 3 retries" : "device reported a malformed stream"; }
             if (!code) {
                 size_t len = b->out.h_img_size[it.image];
                 outputs[n].data = (uint8_t *)malloc(len ? len : 1);

@@ -130,7 +130,8 @@ struct csp_batch {
 
     // WebP conversion
     int webp_quality = 0;
-    uint32_t webp_mb_bytes = 768, wmax_luma = 0, wmax_mbh = 0, rgb_max_h = 0;
+    uint32_t webp_mb_bytes = 768, wmax_luma = 0, wmax_mbh = 0, rgb_max_h = 0;   // webp_mb_bytes: output bytes reserved per macroblock; grows on overflow, CSH_TEST_POOL_SHIFT divides this first value
+    uint32_t last_run_pool_retries = 0;   // how often the last run repeated the encoder with a larger reservation (csp_timing.n_pool_retries)
     uint64_t wwork_bytes = 0, wlevels = 0, rgb_bytes = 0;
     std::vector<csw::WebpImg> wimgs;
     std::vector<csp::RgbJob> rgbjobs;

@@ -28,6 +28,7 @@ int open_device(int device, const CCSParameters *p, int mode, bool from_pixels, 
     b->from_pixels = from_pixels;
     b->decode_only = mode == MODE_DECODE || mode == MODE_DECODE_ANY;
     b->to_webp = mode == MODE_WEBP; b->webp_quality = int(p->webp_quality);
+    b->webp_mb_bytes >>= csh_test_pool_shift();   // (tests: CSH_TEST_POOL_SHIFT, read once per batch object as in batch_plan.cpp layout_token_pool)
     if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) { csh_set_error("hipStreamCreate failed"); return CS_ERR_NO_DEVICE; }
     b->have_stream = true;
     if (b->marks.create()) { csh_set_error("hipEventCreate failed"); return CS_ERR_NO_DEVICE; }

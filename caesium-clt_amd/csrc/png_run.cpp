@@ -64,6 +64,7 @@ void fill_timing(csp_batch *b, csp_timing *t, bool coded) {
         t->n_trials = uint32_t(b->plan.ntrials);
     }
     t->pixels = b->pixels; t->raw_bytes = b->raw_total; t->n_images = uint32_t(b->imgs.size());
+    t->n_pool_retries = b->last_run_pool_retries;
 }
 
 // conversion to WebP: pixels -> 8-bit RGB -> the VP8 encoder of webp_kernels.h (statement: oracle/webp_oracle.c).  The output pool is
@@ -90,10 +91,11 @@ int run_to_webp(csp_batch *b) {
             hipGetLastError() != hipSuccess) { csh_set_error("WebP kernels failed"); return CS_ERR_NO_DEVICE; }
         bool pool = false;
         for (uint32_t s : b->h_wstatus) if (s == CS_ERR_POOL_OVERFLOW) pool = true;
-        if (!pool) break;
-        if (attempt == 3) { csh_set_error("device pools overflowed after 3 retries"); return CS_ERR_POOL_OVERFLOW; }
+        b->last_run_pool_retries = uint32_t(attempt);
+        if (!pool || attempt == 3) break;   // every file has a region of its own: what still does not fit after three retries fails alone (its word in h_wstatus says so), the others are whole
         b->webp_mb_bytes *= 4;
     }
+    csh_count_pool_retries(b->last_run_pool_retries);
     return 0;
 }
 
@@ -209,6 +211,7 @@ extern "C" int csp_batch_run(csp_batch *b, csp_timing *t) {
     if (!b) return CS_ERR_NO_DEVICE;
     if (hipSetDevice(b->device) != hipSuccess) { csh_set_error("hipSetDevice failed"); return CS_ERR_NO_DEVICE; }
     hipStream_t st = b->stream;
+    b->last_run_pool_retries = 0;
     if (!b->reduced && b->d_status.zero(st)) return CS_ERR_NO_DEVICE;
     const FilterCtx f = filter_ctx(b);
     b->marks.start(st);
@@ -239,7 +242,7 @@ extern "C" int csp_batch_fetch(csp_batch *b, CByteArray *outputs, CCSResult *res
         int code = it.code;
         const char *msg = it.msg.c_str();
         if (!code && ai >= 0 && !alpha.out[size_t(ai)].data) { code = int(alpha.res[size_t(ai)].code ? alpha.res[size_t(ai)].code : CS_ERR_NO_DEVICE); msg = "alpha plane coder failed"; }
-        if (!code && !status[it.image] && b->to_webp && b->h_wstatus[it.image]) { code = int(b->h_wstatus[it.image]); msg = "WebP encoder failed"; }
+        if (!code && !status[it.image] && b->to_webp && b->h_wstatus[it.image]) { code = int(b->h_wstatus[it.image]); msg = code == int(CS_ERR_POOL_OVERFLOW) ? "device pools overflowed after 3 retries" : "WebP encoder failed"; }
         else if (!code && status[it.image]) { code = int(status[it.image]); msg = code == int(CSP_ERR_POOL) ? "internal device pool too small" : "malformed PNG data"; }
         if (code) { failed++; if (results) results[i] = png_result(code, msg); continue; }
         const size_t n = flen[it.image];

@@ -158,10 +158,16 @@ typedef struct {
     uint32_t n_dec_walked;        /* sub-sequences a lane of a list round walked on into (up to seven a lane and round), instead of listing them for the next round */
     uint32_t n_dec_chain_scans;   /* scans and restart segments still listed behind the last round, whose block-in-MCU labels the label chain (k_dec_chain) set out to settle */
     uint32_t n_dec_chain_failed;  /* of those, the ones it could not settle: their images went to the sequential kernel and are counted in n_par_fallback */
+    uint32_t n_pool_retries;      /* how often this call ran the batch again with larger output pools because a file did not fit its estimate (0..3).  The grown pools stay with
+                                     the batch object: the same run again reports 0 */
 } csh_timing;
 
 int csh_device_count(void);
 const char *csh_last_error(void);
+/* the sum of n_pool_retries over the batch runs (csh_batch_run, csh_batch_rerun_encode, csp_batch_run) the calling thread has made since it last asked: for the callers of
+   cs_compress_in_memory / cs_convert_in_memory / cs_batch_*, which see no csh_timing.  Reading resets it.  A call that spreads its batches over worker threads (cs_batch_compress
+   over more JPEG files than one span) counts only what ran on the caller's own thread */
+uint32_t csh_last_pool_retries(void);
 void csh_warmup(int device);            /* optional: start the runtime, the device context and the code objects now (call it from a thread of its own while the files are being read) */
 void csh_release_cached_memory(void);   /* hand the cached device pools and pinned blocks of finished batches back to the driver (they are kept for the next batch otherwise) */
 const char *csh_kernel_name(int slot);
@@ -214,6 +220,7 @@ typedef struct {
     uint64_t in_bytes, out_bytes;    /* IDAT bytes in, file bytes out (device result, before the "not smaller" rule) */
     uint64_t pixels, raw_bytes;      /* pixels; bytes of one filtered stream per image, summed */
     uint32_t n_images, n_failed, n_trials;
+    uint32_t n_pool_retries;         /* csp_batch_create_webp: how often this run repeated the VP8 encoder with a larger reservation per macroblock (0..3) */
 } csp_timing;
 const char *csp_kernel_name(int slot);
 int csp_batch_create(const CByteArray *inputs, size_t count, const CCSParameters *p, int device, csp_batch **out);
